@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: images/sec of one SPE training iteration of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = forward (CaiT-S24 TSCAM backbone + 6-layer conditional-DETR decoder, both proposal stages)
@@ -9,6 +9,11 @@ A "step" = forward (CaiT-S24 TSCAM backbone + 6-layer conditional-DETR decoder, 
 -> SetCriterionRefine -> backward -> gradient all-reduce -> clip + AdamW, on synthetic 3x800x1333
 batches of 2 images per GPU (BASELINE.json configs[1]).  Inputs are resident in
 HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times K steps and prints the headline (`value`, `ms_per_step`, the configuration).
+--full adds what takes runs or timers of its own: the per-kernel HIP-event timings and rooflines, the exposed all-reduce
+time, one extra counted step (`kernel_set`), the parity record and the CPU baseline with its loss comparison.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import copy
@@ -213,6 +218,58 @@ def parity_record():
     return obj, prov
 
 
+DUMP_BUDGET = 64 << 20           # bytes over all files of --dump-outputs
+DUMP_SAMPLE = 1 << 20            # elements kept of a larger array: a fixed, seeded sample
+
+
+def _host_array(t, seed=0):
+    """float32 (float64 stays float64) numpy copy of `t`; above DUMP_SAMPLE elements, the values at DUMP_SAMPLE positions drawn with a
+    fixed seed from the flattened array (the positions depend only on its size, so two runs sample the same elements)."""
+    t = t.detach()
+    t = t if t.dtype == torch.float64 else t.float()
+    if t.numel() > DUMP_SAMPLE:
+        idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.cpu().numpy()
+
+
+def dump_outputs(path, last, params, reducer):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy.
+      loss_total                      the weighted total the step returns
+      loss_stage0.<key>, loss_stage1.<key>   every term of SetCriterion / SetCriterionRefine
+      stage<r>.pred_logits / pred_boxes, stage<r>.aux_outputs.<key> (decoder layers stacked)   both proposal stages
+      backbone.<key>                  the backbone outputs both stages share (x_patch: the [B, C, h, w] features)
+      params_sample, grads_sample     the parameters AdamW left behind and the clipped gradients it consumed (model.parameters()
+                                      order, flattened; sampled as in _host_array)
+    Only rank 0 writes; the files stay under DUMP_BUDGET bytes."""
+    import numpy as np
+    total, out, l0, l1 = last
+    arrays = {"loss_total": total}
+    for tag, ld in (("loss_stage0", l0), ("loss_stage1", l1)):
+        for k, v in ld.items():
+            arrays[f"{tag}.{k}"] = torch.as_tensor(v)
+    for r, o in out.items():
+        for k, v in o.items():
+            if k == "aux_outputs":
+                for kk in v[0]:
+                    arrays[f"stage{r}.aux_outputs.{kk}"] = torch.stack([x[kk] for x in v])
+            elif k in ("pred_logits", "pred_boxes"):
+                arrays[f"stage{r}.{k}"] = v
+            elif r == 0:
+                arrays[f"backbone.{k}"] = getattr(v, "tensors", v)
+    with torch.no_grad():
+        arrays["params_sample"] = torch.cat([p.detach().reshape(-1) for p in params])
+        arrays["grads_sample"] = torch.cat([reducer.averaged_grad(p).reshape(-1) for p in params])
+    host = {k: _host_array(v) for k, v in arrays.items()}
+    size = sum(v.nbytes for v in host.values())
+    if size > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {size} bytes over the {DUMP_BUDGET}-byte budget")
+    os.makedirs(path, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return size
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -237,7 +294,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     # gradient wire format of the all-reduce: fp32 (DDP's, the default) or bf16 (half the xGMI bytes, one conversion pass each way)
     ap.add_argument("--wire", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel timings / rooflines, exposed all-reduce time, counted kernel set, parity record and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -307,7 +370,7 @@ def main():
         total.backward()
         reducer.finish()
         opt.step()                      # global-norm clip (0.1) + AdamW, fused on the flat buckets
-        return total
+        return total, out, l0, l1
 
     def sync():
         if world > 1:
@@ -316,7 +379,7 @@ def main():
 
     for _ in range(a.warmup):
         step()
-    # kernels timed live with HIP events on the launch stream: the dominant kernel (the query-major backward kernel of the fused
+    # --full: kernels timed live with HIP events on the launch stream: the dominant kernel (the query-major backward kernel of the fused
     # talking-heads attention: dS, dWl, dbl, dQ), the HBM-bound dK contraction and north_star's decoder cross-attention GEMM (the
     # memory-side projections ca_kcontent / ca_v / ca_kpos of reference models/transformer.py:389-419:
     # [B*S, d] x [d, d] = [8300 x 384] x [384 x 384] at cfg2)
@@ -329,8 +392,9 @@ def main():
     n_dec = args.dec_layers
     CAG_N = 2 * n_dec * d_model          # ca_kcontent + ca_v of all decoder layers in one launch (ops.multi_linear)
     CAG = f"spe_gemm_bf16nt:{S_rows},{CAG_N},{d_model}"
-    K.enable_timing([DOMQ, HBMK, CAG, FLF, STATS, BWDK])
-    reducer.measure = True
+    if a.full:
+        K.enable_timing([DOMQ, HBMK, CAG, FLF, STATS, BWDK])
+        reducer.measure = True
     sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
@@ -338,14 +402,18 @@ def main():
     sync()
     dt_local = time.perf_counter() - t0
     peak_mem = torch.cuda.max_memory_allocated(dev)
-    K_res = K.timing_results()
-    K.enable_timing([])
-    reducer.measure = False
-    # one more (untimed) step with the entry points counted: the kernel set this throughput number belongs to
-    lib.count_launches(True)
-    step()
-    torch.cuda.synchronize()
-    kernel_set = lib.count_launches(False)
+    if a.full:
+        K_res = K.timing_results()
+        K.enable_timing([])
+        reducer.measure = False
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last, params, reducer)
+    if a.full:
+        # one more (untimed) step with the entry points counted: the kernel set this throughput number belongs to
+        lib.count_launches(True)
+        step()
+        torch.cuda.synchronize()
+        kernel_set = lib.count_launches(False)
     per_rank = [dt_local]
     if world > 1:
         tl = torch.tensor([dt_local], device=dev, dtype=torch.float64)
@@ -353,7 +421,7 @@ def main():
         dist.all_gather(gath, tl)
         per_rank = [float(g.item()) for g in gath]
     dt = max(per_rank)
-    loss_val = float(last.detach())
+    loss_val = float(last[0].detach())
     # what the collective actually spanned: backend, group size and every rank's device as the process group reports them (a SCALE
     # line proves its own N), the RCCL version and channel cap, and the exposed all-reduce time of every rank
     exposed = [reducer.exposed_ms_mean()]
@@ -375,45 +443,6 @@ def main():
         imgs = a.batch * world * a.steps
         N = (a.height // 16) * (a.width // 16)
         Hh, dh_ = body.num_heads, body.embed_dim // body.num_heads
-        default_backbone = a.backbone == "TSCAM_cait_S24" and a.height == 800 and a.width == 1333
-        default_cfg = default_backbone and a.queries == 100 and a.batch == 2
-        rin, rin_prov = roofline_inputs()
-        par_all, par_prov = parity_record()
-        kin = rin.get("kernels", {})
-        pk = rin.get("peaks_measured", {})
-        launches, mean_ms = K_res.get(DOMQ, (0, 0.0))
-        # MFMA work of one launch: S = QK^T (a recomputation: SURVEY 8(d) does not count it), dP' = dO V^T (algorithmic) and dQ = dS K
-        # (algorithmic) for all heads, 2*N*N*dh FLOP each.  `achieved` = the algorithmic products, `executed` adds the recomputed S.
-        mf = (2.0 * N * N * dh_) * Hh * a.batch
-        n_alg = 2
-        ach = (n_alg + 1) * mf / (mean_ms * 1e-3) / 1e12 if mean_ms > 0 else 0.0
-        ach_alg = n_alg * mf / (mean_ms * 1e-3) / 1e12 if mean_ms > 0 else 0.0
-        # the PATH's algorithmic FLOPs per image (forward 1.16 TF at enc_layers 0 + 0.044 TF per encoder layer, x3 for fwd + bwd) x images / s
-        path_tf_per_img = 3.0 * (1.16 + 0.0444 * a.enc_layers) if default_backbone else None
-        # vector-pipe work that is left in this pass: the dWl outer product (2*H FLOP per score and head; the three head
-        # mixes run on the matrix pipe since round 2 - S' = Wl S in fp32 on v_mfma_f32_4x4x1, dP and dS in bf16), reported
-        # against the 157.3 TFLOP/s vector peak; exp2 (quarter rate) and the bf16 packing are not counted as FLOP
-        valu_flop = 1 * (2.0 * Hh * Hh) * N * N * a.batch
-        valu = valu_flop / (mean_ms * 1e-3) / 1e12 if mean_ms > 0 else 0.0
-        # second-largest kernel family, HBM-bound: the streaming contractions over the blocked bf16 score tensors
-        # (algorithmic bytes per launch: B*H*N*N*2 B read once; operands/outputs are < 2 % of that)
-        c_launch, c_ms = K_res.get(HBMK, (0, 0.0))
-        c_bytes = 2.0 * a.batch * Hh * N * N
-        c_bw = c_bytes / (c_ms * 1e-3) / 1e9 if c_ms > 0 else 0.0
-        # decoder cross-attention memory-side GEMM: ALGORITHMIC work 2*M*N*K FLOP; in bf16s the forward product runs on
-        # split operands, i.e. the matrix pipe executes 3 MFMAs per algorithmic one and reads hi + lo parts of both operands
-        g_launch, g_ms = K_res.get(CAG, (0, 0.0))
-        # round 4: the memory-side projections run on IEEE fp16 single-term operands and leave as fp16 (ops._MemorySideKV: the consumer
-        # packs fp16 MFMA operands anyway); with SPE_MEMKV=0 / bf16x3 the round-3 path (split bf16 operands in bf16s, fp32 output)
-        from spe_amd import ops as _ops
-        kv16 = _ops.MEMKV and a.precision != "bf16x3"
-        split_fwd = a.precision == "bf16s" and not kv16
-        g_flop = 2.0 * S_rows * CAG_N * d_model
-        g_exec = g_flop * (3.0 if split_fwd else 1.0)
-        g_bytes = (2.0 * S_rows * d_model + 2.0 * CAG_N * d_model) * (2.0 if split_fwd else 1.0) + (2.0 if kv16 else 4.0) * S_rows * CAG_N
-        g_tf = g_flop / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
-        g_bw = g_bytes / (g_ms * 1e-3) / 1e9 if g_ms > 0 else 0.0
-        g_floor_us = max(g_exec / 2.5e15, g_bytes / 8e12) * 1e6
         res = {
             "metric": "images/sec (whole node) at 3x800x1333 bs=2/GPU", "value": imgs / dt, "unit": "images/sec",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
@@ -435,79 +464,121 @@ def main():
                    "stats_pass_workgroups": K.STATS_NWG},
             "dist": dist_info,
             "hbm_peak_allocated_gb": round(peak_mem / 1e9, 2),           # torch allocator high-water mark through the timed steps (of 288 GB)
-            "allreduce_exposed_ms_per_step": max(exposed), "allreduce_exposed_ms_per_rank": exposed,
-            "roofline": {"bound": "mfma",
-                         "kernel": "talking_bwdq_kernel<8,2,tail> + its dQ merge (query-major attention backward: dS, dWl, dbl, dQ = dS K accumulated in registers)",
-                         "launches": launches,
-                         # algorithmic work only (dP' = dO V^T, and dQ = dS K when the flash-skeleton pass ran); the recomputed S = Q K^T is `executed`
-                         "avg_ms": mean_ms, "achieved": ach_alg, "executed": ach, "peak": 2500.0,
-                         "peak_measured": pk.get("mfma_f16_16x16x32_tflops", pk.get("mfma_bf16_tflops")), "unit": "TFLOP/s", "frac": ach_alg / 2500.0,
-                         "frac_executed": ach / 2500.0,
-                         # the whole PATH against the same peak (algorithmic FLOPs per image x images / s / peak)
-                         "path_tflop_per_image": path_tf_per_img,
-                         "path_achieved": (path_tf_per_img * imgs / dt / world) if path_tf_per_img else None,
-                         "path_frac": (path_tf_per_img * imgs / dt / world / 2500.0) if path_tf_per_img else None,
-                         "traffic": kin.get("talking_bwdq_pass2", {}).get("traffic_bytes"),   # bytes/launch, PMC (profiles/roofline_inputs.json)
-                         "traffic_provenance": rin_prov,
-                         "limiter": "instruction issue + exposed waits of ONE wave per SIMD",
-                         "note": ("priced against the MFMA roofline (its arithmetic is matrix work), bound by something else: one wave per SIMD (512 registers: Q / dO "
-                                  "fragments and the 96 dQ accumulators in AccVGPRs) issues in order; per 16x16 tile of all heads ~540 instructions of which 160 are matrix "
-                                  "instructions: the wave issues during ~2600 and keeps the matrix pipe busy ~1800 of the ~5100 cycles a tile takes (SQ counters: "
-                                  "profiles/r06_attn_pmc.txt; region stamps: profiles/r06_bwdq_stamps.txt; DESIGN.md 4.1)"),
-                         "valu_achieved": valu, "valu_peak": 157.3,
-                         "valu_frac": valu / 157.3,
-                         "hbm_kernel": {"bound": "hbm", "kernel": "attn_contract_kernel<3,true,*> (dK = scale dS^T Q: the one streaming read of the blocked bf16 dS)",
-                                        "launches": c_launch, "avg_ms": c_ms, "achieved": c_bw, "peak": 8000.0,
-                                        "peak_measured": pk.get("hbm_read_gbs"), "unit": "GB/s",
-                                        "frac": c_bw / 8000.0, "traffic": kin.get("attn_contract_T", {}).get("traffic_bytes")},
-                         "decoder_ca_gemm": {"kernel": (f"gemm_nt2_kernel<160,128,64,2,single,fp16 operands,fp16 out> " if kv16 else
-                                                        f"gemm_nt2_kernel<128,128,{32 if split_fwd else 64},2,{'split' if split_fwd else 'single'}> ") +
-                                                       f"[{S_rows}x{d_model}]x[{d_model}x{CAG_N}]: ca_kcontent + ca_v projections of the memory for all "
-                                                       f"{n_dec} decoder layers in one launch (the reference runs {2 * n_dec} [{S_rows}x{d_model}]x"
-                                                       f"[{d_model}x{d_model}] GEMMs per decoder pass)",
-                                             "launches": g_launch, "avg_us": g_ms * 1e3, "flop": g_flop, "executed_flop": g_exec, "bytes": g_bytes,
-                                             "achieved_tflops": g_tf, "mfma_frac": g_tf / 2500.0, "executed_mfma_frac": g_exec / max(g_ms, 1e-9) / 1e9 / 2500.0,
-                                             "achieved_gbs": g_bw, "hbm_frac": g_bw / 8000.0, "bound": "epilogue + launch phases beside a 12-step main loop", "floor_us": g_floor_us,
-                                             "note": "north_star's 60 % target is not met (the vendor GEMM: 48-52 us = 23-24 % for this product, tools/debug/mm_peak.py; an A-resident "
-                                                     "persistent kernel measured 55-60 us, profiles/r06_gemm_ares.txt): at K = 384 epilogue and launch phases weigh as much as the "
-                                                     "matrix pipe.  Round 4: IEEE fp16 single-term operands (11 significand bits at bf16's bytes and MFMA rate: "
-                                                     "the keys / values are packed to fp16 MFMA operands by their consumer anyway) and an LDS-staged fp16 output "
-                                                     "(76 MB instead of 153 MB of fp32) - isolated 155 -> 58 us = 503 TFLOP/s = 20 % of the bf16 peak "
-                                                     "(tools/debug/cagemm_check.py), inside the step 154 -> ~78 us (cold operands); main loop ~36 us + stores "
-                                                     "that do not overlap it (profiles/r03_gemm_ablation.txt); parity at cfg2_full / cfg5_full unchanged "
-                                                     "(outputs <= 1.6e-4, weighted loss keys <= 4.4e-4)"}},
-            "precision_contract": par_all.get(a.precision), "precision_contract_provenance": par_prov,
-            # the other attention kernels (no N x N tensor in HBM but the backward's dS), timed live
-            "flash_attention": {"stats": {"launches": K_res.get(STATS, (0, 0.0))[0], "avg_ms": K_res.get(STATS, (0, 0.0))[1]},
-                                "forward": {"launches": K_res.get(FLF, (0, 0.0))[0], "avg_ms": K_res.get(FLF, (0, 0.0))[1]},
-                                # key-major backward kernel: D, dWw, dbw and dV = P'd^T dO in one walk
-                                "bwd_pass1_dv": {"launches": K_res.get(BWDK, (0, 0.0))[0], "avg_ms": K_res.get(BWDK, (0, 0.0))[1]},
-                                "note": "kernel + its partial-result merge(s) per launch; P'd is neither stored nor saved for the backward"},
-            # what ran: entry points of libspe_hip.so launched in one step, and every SPE_* developer knob that was set
-            "kernel_set": dict(sorted(kernel_set.items())),
-            "env_knobs": {k: v for k, v in sorted(os.environ.items()) if k.startswith("SPE_")},
+            "env_knobs": {k: v for k, v in sorted(os.environ.items()) if k.startswith("SPE_")},     # every SPE_* developer knob that was set
         }
-        if world == 1 and not a.no_cpu_baseline and default_cfg:
-            def gpu_eval(img1, mask1, tg1):
-                model.eval(); crit.eval(); crit_r.eval()
+        if a.full:
+            default_backbone = a.backbone == "TSCAM_cait_S24" and a.height == 800 and a.width == 1333
+            default_cfg = default_backbone and a.queries == 100 and a.batch == 2
+            rin, rin_prov = roofline_inputs()
+            par_all, par_prov = parity_record()
+            kin = rin.get("kernels", {})
+            pk = rin.get("peaks_measured", {})
+            launches, mean_ms = K_res.get(DOMQ, (0, 0.0))
+            # MFMA work of one launch: S = QK^T (a recomputation: SURVEY 8(d) does not count it), dP' = dO V^T (algorithmic) and dQ = dS K
+            # (algorithmic) for all heads, 2*N*N*dh FLOP each.  `achieved` = the algorithmic products, `executed` adds the recomputed S.
+            mf = (2.0 * N * N * dh_) * Hh * a.batch
+            n_alg = 2
+            ach = (n_alg + 1) * mf / (mean_ms * 1e-3) / 1e12 if mean_ms > 0 else 0.0
+            ach_alg = n_alg * mf / (mean_ms * 1e-3) / 1e12 if mean_ms > 0 else 0.0
+            # the PATH's algorithmic FLOPs per image (forward 1.16 TF at enc_layers 0 + 0.044 TF per encoder layer, x3 for fwd + bwd) x images / s
+            path_tf_per_img = 3.0 * (1.16 + 0.0444 * a.enc_layers) if default_backbone else None
+            # vector-pipe work that is left in this pass: the dWl outer product (2*H FLOP per score and head; the three head
+            # mixes run on the matrix pipe since round 2 - S' = Wl S in fp32 on v_mfma_f32_4x4x1, dP and dS in bf16), reported
+            # against the 157.3 TFLOP/s vector peak; exp2 (quarter rate) and the bf16 packing are not counted as FLOP
+            valu_flop = 1 * (2.0 * Hh * Hh) * N * N * a.batch
+            valu = valu_flop / (mean_ms * 1e-3) / 1e12 if mean_ms > 0 else 0.0
+            # second-largest kernel family, HBM-bound: the streaming contractions over the blocked bf16 score tensors
+            # (algorithmic bytes per launch: B*H*N*N*2 B read once; operands/outputs are < 2 % of that)
+            c_launch, c_ms = K_res.get(HBMK, (0, 0.0))
+            c_bytes = 2.0 * a.batch * Hh * N * N
+            c_bw = c_bytes / (c_ms * 1e-3) / 1e9 if c_ms > 0 else 0.0
+            # decoder cross-attention memory-side GEMM: ALGORITHMIC work 2*M*N*K FLOP; in bf16s the forward product runs on
+            # split operands, i.e. the matrix pipe executes 3 MFMAs per algorithmic one and reads hi + lo parts of both operands
+            g_launch, g_ms = K_res.get(CAG, (0, 0.0))
+            # round 4: the memory-side projections run on IEEE fp16 single-term operands and leave as fp16 (ops._MemorySideKV: the consumer
+            # packs fp16 MFMA operands anyway); with SPE_MEMKV=0 / bf16x3 the round-3 path (split bf16 operands in bf16s, fp32 output)
+            from spe_amd import ops as _ops
+            kv16 = _ops.MEMKV and a.precision != "bf16x3"
+            split_fwd = a.precision == "bf16s" and not kv16
+            g_flop = 2.0 * S_rows * CAG_N * d_model
+            g_exec = g_flop * (3.0 if split_fwd else 1.0)
+            g_bytes = (2.0 * S_rows * d_model + 2.0 * CAG_N * d_model) * (2.0 if split_fwd else 1.0) + (2.0 if kv16 else 4.0) * S_rows * CAG_N
+            g_tf = g_flop / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
+            g_bw = g_bytes / (g_ms * 1e-3) / 1e9 if g_ms > 0 else 0.0
+            g_floor_us = max(g_exec / 2.5e15, g_bytes / 8e12) * 1e6
+            res.update({
+                "allreduce_exposed_ms_per_step": max(exposed), "allreduce_exposed_ms_per_rank": exposed,
+                "roofline": {"bound": "mfma",
+                             "kernel": "talking_bwdq_kernel<8,2,tail> + its dQ merge (query-major attention backward: dS, dWl, dbl, dQ = dS K accumulated in registers)",
+                             "launches": launches,
+                             # algorithmic work only (dP' = dO V^T, and dQ = dS K when the flash-skeleton pass ran); the recomputed S = Q K^T is `executed`
+                             "avg_ms": mean_ms, "achieved": ach_alg, "executed": ach, "peak": 2500.0,
+                             "peak_measured": pk.get("mfma_f16_16x16x32_tflops", pk.get("mfma_bf16_tflops")), "unit": "TFLOP/s", "frac": ach_alg / 2500.0,
+                             "frac_executed": ach / 2500.0,
+                             # the whole PATH against the same peak (algorithmic FLOPs per image x images / s / peak)
+                             "path_tflop_per_image": path_tf_per_img,
+                             "path_achieved": (path_tf_per_img * imgs / dt / world) if path_tf_per_img else None,
+                             "path_frac": (path_tf_per_img * imgs / dt / world / 2500.0) if path_tf_per_img else None,
+                             "traffic": kin.get("talking_bwdq_pass2", {}).get("traffic_bytes"),   # bytes/launch, PMC (profiles/roofline_inputs.json)
+                             "traffic_provenance": rin_prov,
+                             "limiter": "instruction issue + exposed waits of ONE wave per SIMD",
+                             "note": ("priced against the MFMA roofline (its arithmetic is matrix work), bound by something else: one wave per SIMD (512 registers: Q / dO "
+                                      "fragments and the 96 dQ accumulators in AccVGPRs) issues in order; per 16x16 tile of all heads ~540 instructions of which 160 are matrix "
+                                      "instructions: the wave issues during ~2600 and keeps the matrix pipe busy ~1800 of the ~5100 cycles a tile takes (SQ counters: "
+                                      "profiles/r06_attn_pmc.txt; region stamps: profiles/r06_bwdq_stamps.txt; DESIGN.md 4.1)"),
+                             "valu_achieved": valu, "valu_peak": 157.3,
+                             "valu_frac": valu / 157.3,
+                             "hbm_kernel": {"bound": "hbm", "kernel": "attn_contract_kernel<3,true,*> (dK = scale dS^T Q: the one streaming read of the blocked bf16 dS)",
+                                            "launches": c_launch, "avg_ms": c_ms, "achieved": c_bw, "peak": 8000.0,
+                                            "peak_measured": pk.get("hbm_read_gbs"), "unit": "GB/s",
+                                            "frac": c_bw / 8000.0, "traffic": kin.get("attn_contract_T", {}).get("traffic_bytes")},
+                             "decoder_ca_gemm": {"kernel": (f"gemm_nt2_kernel<160,128,64,2,single,fp16 operands,fp16 out> " if kv16 else
+                                                            f"gemm_nt2_kernel<128,128,{32 if split_fwd else 64},2,{'split' if split_fwd else 'single'}> ") +
+                                                           f"[{S_rows}x{d_model}]x[{d_model}x{CAG_N}]: ca_kcontent + ca_v projections of the memory for all "
+                                                           f"{n_dec} decoder layers in one launch (the reference runs {2 * n_dec} [{S_rows}x{d_model}]x"
+                                                           f"[{d_model}x{d_model}] GEMMs per decoder pass)",
+                                                 "launches": g_launch, "avg_us": g_ms * 1e3, "flop": g_flop, "executed_flop": g_exec, "bytes": g_bytes,
+                                                 "achieved_tflops": g_tf, "mfma_frac": g_tf / 2500.0, "executed_mfma_frac": g_exec / max(g_ms, 1e-9) / 1e9 / 2500.0,
+                                                 "achieved_gbs": g_bw, "hbm_frac": g_bw / 8000.0, "bound": "epilogue + launch phases beside a 12-step main loop", "floor_us": g_floor_us,
+                                                 "note": "north_star's 60 % target is not met (the vendor GEMM: 48-52 us = 23-24 % for this product, tools/debug/mm_peak.py; an A-resident "
+                                                         "persistent kernel measured 55-60 us, profiles/r06_gemm_ares.txt): at K = 384 epilogue and launch phases weigh as much as the "
+                                                         "matrix pipe.  Round 4: IEEE fp16 single-term operands (11 significand bits at bf16's bytes and MFMA rate: "
+                                                         "the keys / values are packed to fp16 MFMA operands by their consumer anyway) and an LDS-staged fp16 output "
+                                                         "(76 MB instead of 153 MB of fp32) - isolated 155 -> 58 us = 503 TFLOP/s = 20 % of the bf16 peak "
+                                                         "(tools/debug/cagemm_check.py), inside the step 154 -> ~78 us (cold operands); main loop ~36 us + stores "
+                                                         "that do not overlap it (profiles/r03_gemm_ablation.txt); parity at cfg2_full / cfg5_full unchanged "
+                                                         "(outputs <= 1.6e-4, weighted loss keys <= 4.4e-4)"}},
+                "precision_contract": par_all.get(a.precision), "precision_contract_provenance": par_prov,
+                # the other attention kernels (no N x N tensor in HBM but the backward's dS), timed live
+                "flash_attention": {"stats": {"launches": K_res.get(STATS, (0, 0.0))[0], "avg_ms": K_res.get(STATS, (0, 0.0))[1]},
+                                    "forward": {"launches": K_res.get(FLF, (0, 0.0))[0], "avg_ms": K_res.get(FLF, (0, 0.0))[1]},
+                                    # key-major backward kernel: D, dWw, dbw and dV = P'd^T dO in one walk
+                                    "bwd_pass1_dv": {"launches": K_res.get(BWDK, (0, 0.0))[0], "avg_ms": K_res.get(BWDK, (0, 0.0))[1]},
+                                    "note": "kernel + its partial-result merge(s) per launch; P'd is neither stored nor saved for the backward"},
+                # what ran: entry points of libspe_hip.so launched in one step
+                "kernel_set": dict(sorted(kernel_set.items())),
+            })
+            if world == 1 and not a.no_cpu_baseline and default_cfg:
+                def gpu_eval(img1, mask1, tg1):
+                    model.eval(); crit.eval(); crit_r.eval()
+                    try:
+                        with torch.no_grad():
+                            tgd = [{k: v.to(dev) for k, v in t.items()} for t in tg1]
+                            o = model(NestedTensor(img1.to(dev), mask1.to(dev)))
+                            e0 = crit(o[0], tgd)
+                            ps = pseudo_labels(rpp, o[0], tgd)
+                            e1 = crit_r(o[1], ps)
+                            keep = ("labels", "boxes", "scores")
+                            return float(weighted_total(e0, e1, wd)), [{k: p[k].detach().cpu() for k in keep} for p in ps]
+                    finally:
+                        model.train(); crit.train(); crit_r.train()
                 try:
-                    with torch.no_grad():
-                        tgd = [{k: v.to(dev) for k, v in t.items()} for t in tg1]
-                        o = model(NestedTensor(img1.to(dev), mask1.to(dev)))
-                        e0 = crit(o[0], tgd)
-                        ps = pseudo_labels(rpp, o[0], tgd)
-                        e1 = crit_r(o[1], ps)
-                        keep = ("labels", "boxes", "scores")
-                        return float(weighted_total(e0, e1, wd)), [{k: p[k].detach().cpu() for k in keep} for p in ps]
-                finally:
-                    model.train(); crit.train(); crit_r.train()
-            try:
-                res["cpu_baseline"], par = cpu_baseline(a.enc_layers, gpu_model=model, gpu_eval=gpu_eval)
-                if par is not None:
-                    res["loss_delta_vs_ref"] = par
-            except Exception as e:      # the CPU leg must never take the GPU number down with it
-                res["cpu_baseline"] = {"value": None, "unit": "images/sec", "cores": host_cores(), "kind": "port",
-                                       "sample": f"failed: {type(e).__name__}: {e}"}
+                    res["cpu_baseline"], par = cpu_baseline(a.enc_layers, gpu_model=model, gpu_eval=gpu_eval)
+                    if par is not None:
+                        res["loss_delta_vs_ref"] = par
+                except Exception as e:      # the CPU leg must never take the GPU number down with it
+                    res["cpu_baseline"] = {"value": None, "unit": "images/sec", "cores": host_cores(), "kind": "port",
+                                           "sample": f"failed: {type(e).__name__}: {e}"}
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,10 +1,11 @@
 #!/bin/bash
 # rocprofv3 kernel statistics of the default bench on the GPU box: tools/prof_stats.sh <tag> [bench args...] -> gpurun_out/<tag>_kernel_stats.csv
 TAG=${1:-prof}; shift
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $OUT/prof_$TAG.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -- python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --full "$@" > $OUT/prof_$TAG.log 2>&1
 f=$(find $OUT/prof_$TAG -name "*kernel_stats.csv" | head -1)
 cp "$f" $OUT/${TAG}_kernel_stats.csv
 find $OUT/prof_$TAG -name "*kernel_trace.csv" -delete

@@ -10,16 +10,16 @@ python -m pytest tests -m gpu -q > $OUT/tests_gpu.log 2>&1
 grep -v "^HIP\|^ROCm\|^Hostname\|^Librccl\|^$" $OUT/tests_gpu.log | tail -3
 python -m pytest tests/test_round6_gpu.py tests/test_round2_gpu.py -m gpu -q -s -k "fp64" 2>&1 | grep "vs fp64" > $OUT/attn_fp64.txt
 python tools/parity_summary.py "round 6 ($TAG)" > $OUT/parity_summary.txt 2>&1; cp profiles/parity_r06.json $OUT/ 2>/dev/null
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-taskset -c 0,1 python bench.py --no-cpu-baseline > $OUT/bench_2cores.json 2>/dev/null
-python bench.py --no-cpu-baseline > $OUT/bench_unpinned.json 2>/dev/null
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+taskset -c 0,1 python bench.py --no-cpu-baseline --full > $OUT/bench_2cores.json 2>/dev/null
+python bench.py --no-cpu-baseline --full > $OUT/bench_unpinned.json 2>/dev/null
 # two ranks on the one GPU over gloo (the data-parallel path end to end: bucketed all-reduce beside the backward, num_boxes all-reduce), fp32 and bf16 wire
-SPE_BENCH_BACKEND=gloo SPE_BENCH_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29711 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_gloo2.json 2>$OUT/bench_gloo2.err
-SPE_BENCH_BACKEND=gloo SPE_BENCH_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29712 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --wire bf16 > $OUT/bench_gloo2_bf16wire.json 2>$OUT/bench_gloo2_bf16wire.err
-python bench.py --enc-layers 3 --no-cpu-baseline > $OUT/bench_enc3.json 2>/dev/null
-python bench.py --backbone TSCAM_cait_S36 --layer-to-det 35 --height 1000 --width 1600 --batch 1 --no-cpu-baseline > $OUT/bench_cfg5.json 2>/dev/null
-python bench.py --enc-layers 3 --queries 300 --drop-path 0.2 --attn-drop 0.05 --backbone-drop 0.07 --no-cpu-baseline > $OUT/bench_script_rates_s24.json 2>$OUT/bench_script_rates_s24.err
-python bench.py --backbone TSCAM_cait_XXS36_Two_Branch --layer-to-det 24 --enc-layers 3 --queries 300 --height 512 --width 512 --batch 1 --drop-path 0.2 --attn-drop 0.05 --backbone-drop 0.07 --no-cpu-baseline > $OUT/bench_script_voc.json 2>$OUT/bench_script_voc.err
+SPE_BENCH_BACKEND=gloo SPE_BENCH_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29711 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --full > $OUT/bench_gloo2.json 2>$OUT/bench_gloo2.err
+SPE_BENCH_BACKEND=gloo SPE_BENCH_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29712 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --full --wire bf16 > $OUT/bench_gloo2_bf16wire.json 2>$OUT/bench_gloo2_bf16wire.err
+python bench.py --enc-layers 3 --no-cpu-baseline --full > $OUT/bench_enc3.json 2>/dev/null
+python bench.py --backbone TSCAM_cait_S36 --layer-to-det 35 --height 1000 --width 1600 --batch 1 --no-cpu-baseline --full > $OUT/bench_cfg5.json 2>/dev/null
+python bench.py --enc-layers 3 --queries 300 --drop-path 0.2 --attn-drop 0.05 --backbone-drop 0.07 --no-cpu-baseline --full > $OUT/bench_script_rates_s24.json 2>$OUT/bench_script_rates_s24.err
+python bench.py --backbone TSCAM_cait_XXS36_Two_Branch --layer-to-det 24 --enc-layers 3 --queries 300 --height 512 --width 512 --batch 1 --drop-path 0.2 --attn-drop 0.05 --backbone-drop 0.07 --no-cpu-baseline --full > $OUT/bench_script_voc.json 2>$OUT/bench_script_voc.err
 python tools/bench_cfg4.py > $OUT/cfg4.json 2> $OUT/cfg4.err
 python tools/debug/attn_time.py > $OUT/attn_time.txt 2>&1
 export TMPDIR=/tmp
