@@ -34,7 +34,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * before any entry point that sums across workgroups, spe_box_loss takes L, spe_linear_small_fwd / _bwd are new; 5 (round 4):
  * the flash-style talking-heads entry points spe_talking_flash_* are new; 6 (round 5): spe_talking_bwdq_* are new; 7 (round 6): ONE attention
  * backward composition - spe_talking_fused(_bits / _plan), spe_attn_merge, spe_talking_flash_rows, spe_talking_flash_dv, spe_talking_bwdq_pass1 removed,
- * spe_talking_stats(_plan) new (the statistics pass alone), spe_rowdot new, spe_layernorm_res_bwd takes dy2 */
+ * spe_talking_stats(_plan) new (the statistics pass alone), spe_rowdot new, spe_layernorm_res_bwd takes dy2.  Still 7 after purely additive
+ * entry points: spe_conv_head_fwd / _plan / _bwd and spe_attn_pmean(_dense) (the woct0head backbones' conv class head and patch-affinity CAMs) */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -311,6 +312,31 @@ int spe_talking_bwdq_pass2(const void* Qf, const void* dOf, const void* Kf, cons
                            const float* c0, const float* Drows, int Np, float* ws_q, float* ws_w, void* dS, float* dq, void* dq16,
                            long ob, long on, long oh, float scale, const void* keepbits, int B, int H, int N, int dh, int nwg, float p_drop,
                            spe_stream_t stream);
+
+/* ---- head-mean of the attention probabilities over heads and blocks (reference models/cait.py:384, 392 - a per-block clone of softmax(proj_l(
+ * scale q k^T)) [B,H,N,N] - stacked and averaged by the woct0head backbone for cams_cls_patch, cait.py:993-994), accumulated without any
+ * [B,H,N,N] tensor: M[b][q][k] += alpha * sum_g P_g[b][q][k] into a caller-owned fp32 M [B,N,N] (alpha = 1 / (depth * H): the mean).
+ * spe_attn_pmean: P_g = exp2(sum_h Wl[g][h] S_h + c0[b][q][g]) recomputed from the fused forward's fp16 Qf / Kf records and the row constants c0
+ *   [B][Np][H] of spe_attn_merge_rows (before proj_w and dropout).  Every 16 x 16 tile of M is read, added to and written by exactly one wave
+ *   (no atomics: launches ordered on the stream give a deterministic sum).  H in {4,8}, head dim <= 64; -2 otherwise.
+ * spe_attn_pmean_dense: the same from a materialised P [B,H,N,ld] (spe_talking_softmax_fwd's P; the fp32 path). */
+int spe_attn_pmean(const void* Qf, const void* Kf, const float* Wl, const float* c0, int Np, float* M, float alpha, int B, int H, int N, int dh,
+                   spe_stream_t stream);
+int spe_attn_pmean_dense(const float* P, float* M, float alpha, int B, int H, int N, long ld, spe_stream_t stream);
+
+/* ---- 3x3 convolutional class head (reference models/cait.py:971-974, 1142-1145, 1309-1312: Conv2d(C, K, 3, padding=1) over the normalised
+ * patch tokens + AdaptiveAvgPool2d(1), and their autograd) as implicit GEMMs on the exact-fp32 matrix instruction, reading the tokens
+ * x [B, h*w, C] channels-last as they are (no permute, no im2col).  W [K][C][3][3], bias [K].  Any B, h, w, K >= 1; C % 4 == 0; -2 otherwise.
+ * spe_conv_head_fwd: map [B,K,h,w] = conv(x) + bias and logits [B,K] = its spatial mean, one launch (the mean crosses workgroups in fixed
+ *   order: needs the reduction workspace, -4 without it).
+ * spe_conv_head_plan: floats of the workspace spe_conv_head_bwd needs for the weight gradient.
+ * spe_conv_head_bwd: with g = dmap + dlogits / (h w) (either may be NULL): dx [B, h*w, C], dW [K][C][3][3], db [K] (any may be NULL), all
+ *   OVERWRITTEN.  dW / db are summed over positions in per-split partial rows of ws, added in split order (no atomics: bitwise reproducible). */
+int spe_conv_head_fwd(const float* x, const float* W, const float* bias, float* map, float* logits, int B, int h, int w, int C, int K,
+                      spe_stream_t stream);
+int spe_conv_head_plan(int B, int h, int w, int C, int K, long* ws_floats);
+int spe_conv_head_bwd(const float* x, const float* W, const float* dmap, const float* dlogits, float* dx, float* dW, float* db, float* ws,
+                      long ws_floats, int B, int h, int w, int C, int K, spe_stream_t stream);
 
 /* ---- streaming contractions of a blocked 16-bit score tensor T (dS of spe_talking_bwdq_pass2):
  *   trans = 0: out[b, q, h, :]   = alpha * sum_key T[b,h][q,key] x[b, key, h, :]   (`attn @ v`, cait.py:388; dQ)

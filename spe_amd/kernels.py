@@ -1546,6 +1546,56 @@ def attn_merge_rows(ws_stats, bl, B, H, N, spw):
     return M, IL, c0
 
 
+def attn_pmean(Qf, Kf, Wl, c0, M, alpha, B, H, N, dh):
+    """M [B,N,N] fp32 += alpha * sum over heads of softmax_k(proj_l(scale q k^T)), recomputed from the fused forward's fp16 fragment records and
+    row constants (csrc/attn_pmean.hip)."""
+    _call("spe_attn_pmean", _p(Qf), _p(Kf), _p(Wl), _p(c0), c0.shape[1], _p(M), float(alpha), B, H, N, dh, _st())
+
+
+def attn_pmean_dense(P, M, alpha, B, H, N, ld):
+    """The same accumulation from the materialised path's P [B,H,N,ld]."""
+    _call("spe_attn_pmean_dense", _p(P), _p(M), float(alpha), B, H, N, ld, _st())
+
+
+def bmm_f32(A, B):
+    """A [Bt, M, Kd] @ B [Bt, Kd, N] (contiguous fp32) on spe_gemm_f32 with 3-term split operands (~fp32 in every precision mode)."""
+    _chk(A, B)
+    Bt, M, Kd = A.shape
+    N = B.shape[2]
+    C = torch.empty((Bt, M, N), device=A.device, dtype=torch.float32)
+    _call("spe_gemm_f32", _p(A), _p(B), _p(C), None, None, M, N, Kd, Kd, N, N, 0, 0, Bt, 1, M * Kd, 0, Kd * N, 0, M * N, 0,
+          1.0, 0, 1, 1, _st())
+    return C
+
+
+def conv_head_fwd(x3, W, b, h, w):
+    """x3 [B, h*w, C] contiguous fp32 tokens (channels-last), W [K,C,3,3], b [K] -> (map [B,K,h,w], logits [B,K] = spatial mean of map)."""
+    _chk(x3, W, b)
+    B, hw, C = x3.shape
+    Kc = W.shape[0]
+    assert hw == h * w and x3.is_contiguous() and W.is_contiguous() and b.is_contiguous()
+    m = torch.empty((B, Kc, h, w), device=x3.device, dtype=torch.float32)
+    lg = torch.empty((B, Kc), device=x3.device, dtype=torch.float32)
+    _call("spe_conv_head_fwd", _p(x3), _p(W), _p(b), _p(m), _p(lg), B, h, w, C, Kc, _st())
+    return m, lg
+
+
+def conv_head_bwd(x3, W, dmap, dlogits, h, w, need_dx=True, dW_out=None, db_out=None):
+    """Gradients of conv_head_fwd for g = dmap + dlogits / (h w) (either may be None) -> (dx [B, h*w, C] or None, dW [K,C,3,3], db [K]); dW / db
+    are written (not accumulated) into dW_out / db_out when given."""
+    _chk(x3, W, dmap, dlogits)
+    B, hw, C = x3.shape
+    Kc = W.shape[0]
+    n = ctypes.c_long(0)
+    lib.call("spe_conv_head_plan", B, h, w, C, Kc, ctypes.byref(n))
+    ws = torch.empty((n.value,), device=x3.device, dtype=torch.float32)
+    dx = torch.empty_like(x3) if need_dx else None
+    dW = dW_out.view(W.shape) if dW_out is not None else torch.empty_like(W)
+    db = db_out.view(-1) if db_out is not None else torch.empty((Kc,), device=x3.device, dtype=torch.float32)
+    _call("spe_conv_head_bwd", _p(x3), _p(W), _p(dmap), _p(dlogits), _p(dx), _p(dW), _p(db), _p(ws), n.value, B, h, w, C, Kc, _st())
+    return dx, dW, db
+
+
 def jitter_pick(box, scale, ratio):
     """box [M,4] cxcywh, scale [M,ncand,4] uniform factors -> [M, ratio, 4]: the first ratio - 1 candidates with IoU > 0.7, original last."""
     _chk(box, scale)

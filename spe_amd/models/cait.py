@@ -78,16 +78,17 @@ class Attention_talking_head(nn.Module):
         self.proj_w = nn.Linear(num_heads, num_heads)
         self.proj_drop = Dropout(proj_drop)
 
-    def context(self, x):
-        """Attention output before the output projection."""
+    def context(self, x, acc=None):
+        """Attention output before the output projection.  acc: None or (M, alpha) - the head sum of the attention probabilities is added into
+        M [B,N,N] (ops.talking_heads_attention)."""
         if ops.qkv_talking_attention_ok(x, self.qkv.weight, self.qkv.bias, self.num_heads):
             # qkv Linear + attention as one autograd node: the gradient w.r.t. qkv only exists as the bf16 GEMM operand
             return ops.qkv_talking_attention(x, self.qkv.weight, self.qkv.bias, self.proj_l.weight, self.proj_l.bias, self.proj_w.weight,
-                                             self.proj_w.bias, self.num_heads, self.scale, self.attn_drop if self.training else 0.0)
+                                             self.proj_w.bias, self.num_heads, self.scale, self.attn_drop if self.training else 0.0, acc=acc)
         qkv = self.qkv(x)
         return ops.talking_heads_attention(qkv, self.proj_l.weight, self.proj_l.bias, self.proj_w.weight,
                                            self.proj_w.bias, self.num_heads, self.scale,
-                                           self.attn_drop if self.training else 0.0)
+                                           self.attn_drop if self.training else 0.0, acc=acc)
 
     def forward(self, x):
         return self.proj_drop(self.proj(self.context(x)))
@@ -107,9 +108,10 @@ class LayerScale_Block(nn.Module):
         self.gamma_1 = nn.Parameter(init_values * torch.ones(dim))
         self.gamma_2 = nn.Parameter(init_values * torch.ones(dim))
 
-    def forward(self, x, single_out=False):
+    def forward(self, x, single_out=False, acc=None):
         """single_out: the caller promises that the block's output feeds ONE LayerNorm-skip node (the next block's norm1) and nothing else - its
-        LayerScale backward then rides on that norm's backward (ops._LayerNormSkip); the attention branch's output always does (norm2 below)."""
+        LayerScale backward then rides on that norm's backward (ops._LayerNormSkip); the attention branch's output always does (norm2 below).
+        acc: see Attention_talking_head.context."""
         B = x.shape[0]
         # norm.skip(x) -> (LN(x), x): the residual operand comes back through the LayerNorm node, whose backward kernel
         # adds the skip-path gradient to the normalisation's (one launch less per branch than autograd's sum)
@@ -118,9 +120,10 @@ class LayerScale_Block(nn.Module):
         y, xs = self.norm1.skip(x) if skip else (self.norm1(x), x)
         if isinstance(self.attn, Attention_talking_head):
             # output projection (+ proj_drop) + DropPath + LayerScale residual as one node (same arithmetic, same dropout stream)
-            x = ops.linear_residual(self.attn.context(y), self.attn.proj.weight, self.attn.proj.bias, xs, self.gamma_1, ss1,
+            x = ops.linear_residual(self.attn.context(y, acc), self.attn.proj.weight, self.attn.proj.bias, xs, self.gamma_1, ss1,
                                     self.attn.proj_drop.p if self.training else 0.0, single=skip)
         else:
+            assert acc is None, "the attention-map accumulator needs Attention_talking_head"
             x = ops.layerscale_residual(xs, self.attn(y), self.gamma_1, ss1)
         ss = ops.drop_path_scale(B, self.drop_path, self.training, x.device)
         # the MLP of precision mode bf16s runs its forward products on fp16 operands: its LayerNorm emits the fp16 copy instead of the low part
@@ -139,9 +142,10 @@ def _skip_norms(blk):
 
 
 class Multi_Class_Attention(nn.Module):
-    """Class attention with K+1 class tokens as queries; the softmax map is kept (it becomes the CAMs)."""
+    """Class attention with the class tokens as queries - K+1 by default, num_queries = K for the backbones without the leading class token
+    (Multi_Class_Attention_WithoutCT0, reference cait.py:142-187); the softmax map is kept (it becomes the CAMs)."""
 
-    def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0.0, proj_drop=0.0, num_classes=20):
+    def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0.0, proj_drop=0.0, num_classes=20, num_queries=None):
         super().__init__()
         self.num_heads = num_heads
         self.scale = qk_scale or (dim // num_heads) ** -0.5
@@ -152,6 +156,7 @@ class Multi_Class_Attention(nn.Module):
         self.proj = Linear(dim, dim)
         self.proj_drop = Dropout(proj_drop)
         self.num_classes = num_classes
+        self.num_queries = num_classes + 1 if num_queries is None else num_queries
         self.attention_map = None
 
     def get_attention_map(self):
@@ -159,7 +164,7 @@ class Multi_Class_Attention(nn.Module):
 
     def forward(self, x, **kwargs):
         B, N, C = x.shape
-        H, n_tok = self.num_heads, self.num_classes + 1
+        H, n_tok = self.num_heads, self.num_queries
         q = self.q(x[:, :n_tok]).view(B, n_tok, H, C // H)
         k = self.k(x).view(B, N, H, C // H)
         v = self.v(x).view(B, N, H, C // H)
@@ -171,11 +176,11 @@ class Multi_Class_Attention(nn.Module):
 class LayerScale_Block_CA_MultiClass(nn.Module):
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=False, qk_scale=None, drop=0.0, attn_drop=0.0,
                  drop_path=0.0, act_layer=None, norm_layer=LayerNorm, Attention_block=Multi_Class_Attention,
-                 Mlp_block=Mlp, init_values=1e-4, num_classes=20):
+                 Mlp_block=Mlp, init_values=1e-4, num_classes=20, num_queries=None):
         super().__init__()
         self.norm1 = norm_layer(dim)
         self.attn = Attention_block(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale,
-                                    attn_drop=attn_drop, proj_drop=drop, num_classes=num_classes)
+                                    attn_drop=attn_drop, proj_drop=drop, num_classes=num_classes, num_queries=num_queries)
         self.drop_path = float(drop_path)
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp_block(in_features=dim, hidden_features=int(dim * mlp_ratio), drop=drop)
@@ -195,6 +200,7 @@ class LayerScale_Block_CA_MultiClass(nn.Module):
 
 class _TSCAMBase(nn.Module):
     """Shared construction of cait_models (cait.py:421-516) + the TSCAM additions."""
+    cls_offset = 1          # class tokens in front of the K per-class tokens (the class-attention queries are K + cls_offset)
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4.0, qkv_bias=False, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0,
@@ -216,7 +222,7 @@ class _TSCAMBase(nn.Module):
         self.blocks_token_only = nn.ModuleList([
             LayerScale_Block_CA_MultiClass(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio_clstk, qkv_bias=qkv_bias,
                                            qk_scale=qk_scale, drop=0.0, attn_drop=0.0, drop_path=0.0, norm_layer=norm_layer,
-                                           init_values=init_scale, num_classes=num_classes)
+                                           init_values=init_scale, num_classes=num_classes, num_queries=num_classes + self.cls_offset)
             for _ in range(depth_token_only)])
         self.norm = norm_layer(embed_dim)
         self.head = Linear(embed_dim, num_classes) if num_classes > 0 else nn.Identity()   # unused, kept for checkpoints
@@ -269,8 +275,10 @@ class _TSCAMBase(nn.Module):
         tok = self.patch_embed(x)
         pe = self.InterpolateInitPosEmbed(self.pos_embed, img_size=(H, W))
         tok = self.pos_drop(ops.add_rows(tok, pe[0].contiguous()))
-        cls = torch.cat((self.cls_token.expand(B, -1, -1), self.extra_cls_token.expand(B, -1, -1)), dim=1)
-        return tok, cls.contiguous()
+        return tok, self._cls_tokens(B).contiguous()
+
+    def _cls_tokens(self, B):
+        return torch.cat((self.cls_token.expand(B, -1, -1), self.extra_cls_token.expand(B, -1, -1)), dim=1)
 
     def _heads(self, x, cls_tokens):
         for blk in self.blocks_token_only:
@@ -333,20 +341,25 @@ class TSCAM_cait_two_branch(_TSCAMBase):
         for i in range(1, 1 + len(self.blocks_det)):
             self.blocks_det[-i].load_state_dict(self.blocks[-i].state_dict(), strict=True)
 
+    def _branches(self, x, acc=None):
+        """Main branch through all `depth` blocks and the detection branch (blocks_det + norm_det from block `layer_to_det` on) -> (x, x_feat).
+        acc: passed to the main branch's blocks (Attention_talking_head.context)."""
+        x_feat = None
+        nb, nd = len(self.blocks), len(self.blocks_det)
+        for i, blk in enumerate(self.blocks):
+            x = blk(x, single_out=(i + 1 != self.layer_to_det and i + 1 < nb and _skip_norms(self.blocks[i + 1])), acc=acc)
+            if i + 1 == self.layer_to_det:
+                x_feat = x
+        for i, blk in enumerate(self.blocks_det):
+            x_feat = blk(x_feat, single_out=(i + 1 < nd and _skip_norms(self.blocks_det[i + 1])))
+        return x, self.norm_det(x_feat)
+
     def forward(self, tensor_list):
         x, _ = tensor_list.decompose()
         B, _, H, W = x.shape
         hw = (H // self.patch_size, W // self.patch_size)
         x, cls_tokens = self._embed(x)
-        x_feat = None
-        nb, nd = len(self.blocks), len(self.blocks_det)
-        for i, blk in enumerate(self.blocks):
-            x = blk(x, single_out=(i + 1 != self.layer_to_det and i + 1 < nb and _skip_norms(self.blocks[i + 1])))
-            if i + 1 == self.layer_to_det:
-                x_feat = x
-        for i, blk in enumerate(self.blocks_det):
-            x_feat = blk(x_feat, single_out=(i + 1 < nd and _skip_norms(self.blocks_det[i + 1])))
-        x_feat = self.norm_det(x_feat)
+        x, x_feat = self._branches(x)
         x_logits, x_cls_logits = self._heads(x, cls_tokens)
         K = self.num_classes
         with torch.no_grad():
@@ -356,6 +369,73 @@ class TSCAM_cait_two_branch(_TSCAMBase):
             std = std / std.max(dim=1, keepdim=True)[0]
             cams = (cam * std).sum(1).reshape(B, K, hw[0], hw[1])
         return self._pack(x_logits, x_cls_logits, cams, x_feat, hw)
+
+
+class _TSCAMConvHead(TSCAM_cait_two_branch):
+    """The woct0head family (cait.py:834-1332): TSCAM_cait_two_branch's two branches with a 3x3 convolutional class head over the normalised
+    patch tokens - conv_head + spatial mean = x_cls_logits (trained through the image-label loss) - in place of cls_head_multi_cls, and
+    cams_cls = relu(head-mean class-attention map x conv map).  The variants differ in their class tokens:
+      v1: extra_cls_token [1, K+1, C] (cls_token exists, unused), K+1 queries, patch tokens from K+1, + cams_cls_patch (cait.py:993-997)
+      v2: extra_cls_token [1, K, C], K queries (Multi_Class_Attention_WithoutCT0), patch tokens from K
+      v3: cat(cls_token, extra_cls_token [1, K, C]), K+1 queries, patch tokens from K+1
+    cams_cls_patch contracts the class-to-patch map with the mean of every main-branch block's softmax(proj_l(q k^T)) over heads and blocks;
+    the reference stacks a [B,H,N,N] clone per block (cait.py:384, 392), here one [B,N,N] accumulator receives each block's head sum
+    (csrc/attn_pmean.hip)."""
+    extra_tokens = 0        # extra_cls_token rows beyond K
+    use_cls_token = False   # cls_token heads the class tokens
+    patch_cams = False      # cams_cls_patch
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        del self.cls_head_multi_cls
+        K, C = self.num_classes, self.embed_dim
+        self.extra_cls_token = nn.Parameter(torch.zeros(1, K + self.extra_tokens, C))
+        trunc_normal_(self.extra_cls_token, std=0.02)
+        self.conv_head = nn.Conv2d(C, K, 3, padding=1)            # parameters only: csrc/conv_head.hip
+
+    def _cls_tokens(self, B):
+        ext = self.extra_cls_token.expand(B, -1, -1)
+        return torch.cat((self.cls_token.expand(B, -1, -1), ext), dim=1) if self.use_cls_token else ext
+
+    def forward(self, tensor_list):
+        x, _ = tensor_list.decompose()
+        B, _, H, W = x.shape
+        hw = (H // self.patch_size, W // self.patch_size)
+        x, cls_tokens = self._embed(x)
+        acc = None
+        if self.patch_cams:
+            N = x.shape[1]
+            acc = (torch.zeros((B, N, N), device=x.device, dtype=torch.float32), 1.0 / (len(self.blocks) * self.num_heads))
+        x, x_feat = self._branches(x, acc)
+        for blk in self.blocks_token_only:
+            cls_tokens = blk(x, cls_tokens)
+        K, o = self.num_classes, self.cls_offset
+        # LayerNorm is per token: the class tokens and the patch tokens are normalised separately (no [B, n + N, C] concatenation)
+        x_logits = self.cls_head(self.norm(cls_tokens)[:, o:o + K]).squeeze(-1)
+        x_map, x_cls_logits = ops.conv_head(self.norm(x), self.conv_head.weight, self.conv_head.bias, hw)
+        with torch.no_grad():
+            cw = self.blocks_token_only[0].attn.get_attention_map().mean(1)[:, o:o + K, o + K:]      # [B, K, N]
+            cams = F.relu(cw.reshape(B, K, hw[0], hw[1]) * x_map)
+            if self.patch_cams:
+                cp = ops.bmm_f32(cw.contiguous(), acc[0])                                              # einsum('bci,bij->bcj')
+                cams_patch = F.relu(cp.reshape(B, K, hw[0], hw[1]) * x_map)
+        out = self._pack(x_logits, x_cls_logits, cams, x_feat, hw)          # x_patch keeps its graph: outside no_grad
+        if self.patch_cams:
+            out["cams_cls_patch"] = cams_patch
+        return out
+
+
+class TSCAM_cait_two_branch_conv_cls_attn_woct0head(_TSCAMConvHead):
+    extra_tokens = 1
+    patch_cams = True
+
+
+class TSCAM_cait_two_branch_conv_cls_attn_woct0head_v2(_TSCAMConvHead):
+    cls_offset = 0
+
+
+class TSCAM_cait_two_branch_conv_cls_attn_woct0head_v3(_TSCAMConvHead):
+    use_cls_token = True
 
 
 # ------------------------------------------------------------------------------------------------
@@ -392,6 +472,30 @@ def _make(cls, width, depth, heads, init_scale, pretrained, ckpt=None, img_size=
 @register_model
 def TSCAM_cait_XXS24(pretrained=False, **kw):
     return _make(TSCAM_cait, 192, 24, 4, 1e-5, pretrained, **kw)
+
+
+@register_model
+def TSCAM_cait_XXS24_224(pretrained=False, **kw):
+    """cait.py:1383-1417: TSCAM_cait with the XXS24 dimensions on the 224 x 224 position grid."""
+    return _make(TSCAM_cait, 192, 24, 4, 1e-5, pretrained, img_size=224, **kw)
+
+
+@register_model
+def TSCAM_cait_XXS36_Two_Branch_conv_cls_attn_woct0head(pretrained=False, **kw):
+    """cait.py:1667-1701."""
+    return _make(TSCAM_cait_two_branch_conv_cls_attn_woct0head, 192, 36, 4, 1e-5, pretrained, **kw)
+
+
+@register_model
+def TSCAM_cait_XXS36_Two_Branch_conv_cls_attn_woct0head_v2(pretrained=False, **kw):
+    """cait.py:1704-1738."""
+    return _make(TSCAM_cait_two_branch_conv_cls_attn_woct0head_v2, 192, 36, 4, 1e-5, pretrained, **kw)
+
+
+@register_model
+def TSCAM_cait_XXS36_Two_Branch_conv_cls_attn_woct0head_v3(pretrained=False, **kw):
+    """cait.py:1741-1775."""
+    return _make(TSCAM_cait_two_branch_conv_cls_attn_woct0head_v3, 192, 36, 4, 1e-5, pretrained, **kw)
 
 
 @register_model

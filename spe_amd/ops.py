@@ -428,11 +428,11 @@ def dropout(x, p, training):
 class _TalkingHeadsAttention(Function):
     """CaiT talking-heads self-attention core (reference models/cait.py:377-389): qkv [B,N,3C] ->
     out [B,N,C].  Materialised-score implementation: QK^T GEMM -> fused head-mix/softmax/head-mix/
-    dropout row kernel -> PV GEMM; the saved tensors are P and Pd ([B,H,N,N] each)."""
+    dropout row kernel -> PV GEMM; the saved tensors are P and Pd ([B,H,N,N] each).  acc: see talking_heads_attention."""
 
     @staticmethod
     @K.forward_scope
-    def forward(ctx, qkv, Wl, bl, Ww, bw, H, scale, p_drop):
+    def forward(ctx, qkv, Wl, bl, Ww, bw, H, scale, p_drop, acc=None):
         B, N, C3 = qkv.shape
         C = C3 // 3
         dh = C // H
@@ -446,6 +446,8 @@ class _TalkingHeadsAttention(Function):
         K.gemm(q, k, S, N, N, dh, C3, C3, ld, False, True, batch0=B, batch1=H, sA=sq, sB=sq, sC=sS, alpha=scale)
         seed, off = K.next_rng() if p_drop > 0 else (0, 0)
         P, Pd = K.talking_fwd(S, Wl, bl, Ww, bw, B, H, N, N, ld, p_drop, seed, off)
+        if acc is not None:
+            K.attn_pmean_dense(P, acc[0], acc[1], B, H, N, ld)
         O = torch.empty((B, N, C), device=qkv.device, dtype=torch.float32)
         K.gemm(Pd, v, O, N, dh, N, ld, C3, C, False, False, batch0=B, batch1=H, sA=sS, sB=sq, sC=(N * C, dh))
         ctx.meta = (B, N, C, H, dh, ld, scale, p_drop, seed, off)
@@ -477,7 +479,7 @@ class _TalkingHeadsAttention(Function):
         # dQ = scale * dS K ; dK = scale * dS^T Q
         K.gemm(dS, k, dq, N, dh, N, ld, C3, C3, False, False, batch0=B, batch1=H, sA=sS, sB=sq, sC=sq, alpha=scale)
         K.gemm(dS, q, dk, N, dh, N, ld, C3, C3, True, False, batch0=B, batch1=H, sA=sS, sB=sq, sC=sq, alpha=scale)
-        return dqkv, dWl, dbl, dWw, dbw, None, None, None
+        return dqkv, dWl, dbl, dWw, dbw, None, None, None, None
 
 
 class _TalkingHeadsAttentionFused(Function):
@@ -491,16 +493,17 @@ class _TalkingHeadsAttentionFused(Function):
 
     @staticmethod
     @K.forward_scope
-    def forward(ctx, qkv, Wl, bl, Ww, bw, H, scale, p_drop):
+    def forward(ctx, qkv, Wl, bl, Ww, bw, H, scale, p_drop, acc=None):
         train = any(ctx.needs_input_grad)
-        O, saved = _TalkingHeadsAttentionFused._fwd(ctx, qkv, Wl, bl, Ww, bw, H, scale, p_drop, train)
+        O, saved = _TalkingHeadsAttentionFused._fwd(ctx, qkv, Wl, bl, Ww, bw, H, scale, p_drop, train, acc)
         if train:
             ctx.save_for_backward(*saved)
         return O
 
     @staticmethod
-    def _fwd(ctx, qkv, Wl, bl, Ww, bw, H, scale, p_drop, train):
-        """-> (O, tensors the backward needs); also used by _QkvTalkingAttention (the qkv Linear inside the same node)."""
+    def _fwd(ctx, qkv, Wl, bl, Ww, bw, H, scale, p_drop, train, acc=None):
+        """-> (O, tensors the backward needs); also used by _QkvTalkingAttention (the qkv Linear inside the same node).  acc: see
+        talking_heads_attention."""
         B, N, C3 = qkv.shape
         C = C3 // 3
         dh = C // H
@@ -524,6 +527,8 @@ class _TalkingHeadsAttentionFused(Function):
         K.talking_stats(Qf, Kf, Wl, bl, ws_stats, B, H, N, dh)
         want16 = K.produces16(B * N, C)
         _, _, c0 = K.attn_merge_rows(ws_stats, bl, B, H, N, spw0)
+        if acc is not None:
+            K.attn_pmean(Qf, Kf, Wl, c0, acc[0], acc[1], B, H, N, dh)
         # P' goes from the head mix straight into the P' V products: nothing N x N is stored or saved - the backward recomputes it
         O, O16, O16lo, bits = K.talking_flash_fwd(Qf, Kf, V16, Wl, Ww, bw, c0, B, H, N, dh, p_drop, seed, off, want16, K.split_fwd(),
                                                   want_bits=True)
@@ -539,7 +544,7 @@ class _TalkingHeadsAttentionFused(Function):
     @staticmethod
     @K.backward_scope
     def backward(ctx, dO):
-        return (*_TalkingHeadsAttentionFused._bwd(ctx, ctx.saved_tensors, dO, False), None, None, None)
+        return (*_TalkingHeadsAttentionFused._bwd(ctx, ctx.saved_tensors, dO, False), None, None, None, None)
 
     @staticmethod
     def _bwd(ctx, saved, dO, out16):
@@ -574,13 +579,13 @@ class _QkvTalkingAttention(Function):
 
     @staticmethod
     @K.forward_scope
-    def forward(ctx, x, Wq, bq, Wl, bl, Ww, bw, H, scale, p_drop):
+    def forward(ctx, x, Wq, bq, Wl, bl, Ww, bw, H, scale, p_drop, acc=None):
         shp = x.shape
         x2 = x.reshape(-1, shp[-1])
         if not x2.is_contiguous():
             x2 = x2.contiguous()
         y, _, xsave = K.linear_fwd(x2, Wq, bq, 0, want_pre=False, save_for_dw=True, src=x)
-        O, saved = _TalkingHeadsAttentionFused._fwd(ctx, y.view(*shp[:-1], Wq.shape[0]), Wl, bl, Ww, bw, H, scale, p_drop, True)
+        O, saved = _TalkingHeadsAttentionFused._fwd(ctx, y.view(*shp[:-1], Wq.shape[0]), Wl, bl, Ww, bw, H, scale, p_drop, True, acc)
         ctx.qparams = (Wq, bq)
         ctx.save_for_backward(xsave, *saved)
         return O
@@ -604,7 +609,7 @@ class _QkvTalkingAttention(Function):
             dx = torch.empty((R, Kd), device=dev, dtype=torch.float32)
             K.gemm16(d16, K.weight16(Wq)[1], dx, R, Kd, N3, N3, N3, Kd)
             dx = dx.view(*dO.shape[:-1], Kd)
-        return dx, dW, db.view_as(bq), dWl, dbl, dWw, dbw, None, None, None
+        return dx, dW, db.view_as(bq), dWl, dbl, dWw, dbw, None, None, None, None
 
 
 QKV_FUSED = True        # module attribute, not an environment knob
@@ -620,8 +625,8 @@ def qkv_talking_attention_ok(x, Wq, bq, num_heads):
             and K.fused_supported(num_heads, C // num_heads))
 
 
-def qkv_talking_attention(x, Wq, bq, Wl, bl, Ww, bw, num_heads, scale, p_drop=0.0):
-    return _QkvTalkingAttention.apply(x, Wq, bq, Wl, bl, Ww, bw, num_heads, scale, p_drop)
+def qkv_talking_attention(x, Wq, bq, Wl, bl, Ww, bw, num_heads, scale, p_drop=0.0, acc=None):
+    return _QkvTalkingAttention.apply(x, Wq, bq, Wl, bl, Ww, bw, num_heads, scale, p_drop, acc)
 
 
 class _MlpGelu(Function):
@@ -817,14 +822,55 @@ def mlp_gelu(x, W1, b1, W2, b2):
     return linear(linear(x, W1, b1, ACT_GELU), W2, b2)
 
 
-def talking_heads_attention(qkv, Wl, bl, Ww, bw, num_heads, scale, p_drop=0.0, fused=None):
+def talking_heads_attention(qkv, Wl, bl, Ww, bw, num_heads, scale, p_drop=0.0, fused=None, acc=None):
     """fused=None: use the fused kernels in the bf16 / bf16s modes when the head geometry is supported (their forward runs
-    on fp16 operands in both modes, csrc/attn_fused.hip); the 3-term (bf16x3) parity mode keeps the fp32 materialised path."""
+    on fp16 operands in both modes, csrc/attn_fused.hip); the 3-term (bf16x3) parity mode keeps the fp32 materialised path.
+    acc: None, or (M, alpha) - M [B,N,N] fp32 += alpha * sum over heads of this block's softmax(proj_l(scale q k^T)) (taken before proj_w and
+    dropout: reference models/cait.py:384, the map the woct0head backbone averages over heads and blocks for cams_cls_patch).  No gradient."""
     dh = qkv.shape[-1] // (3 * num_heads)
     if fused is None:
         fused = K.get_precision() != "bf16x3" and K.fused_supported(num_heads, dh)
     fn = _TalkingHeadsAttentionFused if fused else _TalkingHeadsAttention
-    return fn.apply(qkv, Wl, bl, Ww, bw, num_heads, scale, p_drop)
+    return fn.apply(qkv, Wl, bl, Ww, bw, num_heads, scale, p_drop, acc)
+
+
+# ---------------------------------------------------------------------------------------------
+class _ConvHead(Function):
+    """Conv2d(C, K, 3, padding=1) over the patch tokens + AdaptiveAvgPool2d(1) (reference models/cait.py:971-974 of the woct0head backbones)
+    as one node on csrc/conv_head.hip: x [B, h*w, C] tokens as they are (channels-last) -> (map [B,K,h,w], logits [B,K]).  Its backward takes the
+    gradients of both outputs in one pass (the pooled one spread over the positions inside the kernels) and returns dx into the LayerNorm's
+    backward; exact fp32 in every precision mode."""
+
+    @staticmethod
+    @K.forward_scope
+    def forward(ctx, x, W, b, h, w):
+        x = x.contiguous()
+        m, lg = K.conv_head_fwd(x, W, b, h, w)
+        ctx.hw = (h, w)
+        ctx.params = (W, b)
+        ctx.save_for_backward(x, W)
+        return m, lg
+
+    @staticmethod
+    @K.backward_scope
+    def backward(ctx, dmap, dlog):
+        x, W = ctx.saved_tensors
+        h, w = ctx.hw
+        dmap = dmap.contiguous() if dmap is not None else None
+        dlog = dlog.contiguous() if dlog is not None else None
+        Wp, bp = ctx.params
+        dx, dW, db = K.conv_head_bwd(x, W, dmap, dlog, h, w, ctx.needs_input_grad[0], K.grad_buffer(Wp), K.grad_buffer(bp))
+        return dx, dW, db, None, None
+
+
+def bmm_f32(A, B):
+    """A [Bt,M,K] @ B [Bt,K,N] without gradient (the woct0head backbone's cams_cls_patch einsum, reference models/cait.py:995)."""
+    return K.bmm_f32(A.contiguous(), B.contiguous())
+
+
+def conv_head(x, W, b, hw):
+    """(map [B,K,h,w], pooled logits [B,K]) of the 3x3 class head over the tokens x [B, h*w, C]."""
+    return _ConvHead.apply(x, W, b, int(hw[0]), int(hw[1]))
 
 
 # ---------------------------------------------------------------------------------------------
