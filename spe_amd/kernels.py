@@ -293,8 +293,7 @@ def _chk(*ts):
             raise TypeError(f"expected float32, got {t.dtype}")
 
 
-TN_SMALL_TILES = True     # 64 x 64 tiles for weight gradients with few output tiles (module attributes, not environment knobs)
-TN_SMALL_MAX = 256
+TN_SMALL_MAX = 256        # 64 x 64 tiles for weight gradients with fewer 128-tiles x splits than this
 
 
 def auto_splitk(M, N, K, batch):
@@ -307,7 +306,7 @@ def auto_splitk(M, N, K, batch):
     # tiles * splits must FIT the 512 resident workgroup slots (2 per CU): 36 tiles x 15 = 540 leaves 28 workgroups for a
     # second, nearly empty round (fc1 / fc2 dW: 29 -> 24 us with 14 splits)
     sk = max(1, min(512 // tiles, K // 512, 16))
-    if TN_SMALL_TILES and batch == 1 and tiles * sk < TN_SMALL_MAX:
+    if batch == 1 and tiles * sk < TN_SMALL_MAX:
         # few output tiles even at the largest split (a 384 x 384 weight: 9 tiles x 16 = 144 workgroups on 512 slots): 64 x 64 tiles
         # (spe_gemm_bf16tn picks them when 128-tiles x splits < 256) quadruple the tile count; the split is sized for THEM
         t64 = ((M + 63) // 64) * ((N + 63) // 64)
@@ -342,15 +341,12 @@ def weights_changed():
     _W16_EPOCH += 1
 
 
-
-LINEAR_SMALL = True
 LINEAR_SMALL_MAX_ROWS = 2048
 
 
 def _lin_small_ok(R, N, K):
-    """The one-launch Linear of csrc/linear_small.hip: row-major bf16 saves (DW_TN), 128 <= rows < 2048."""
-    return (LINEAR_SMALL and DW_TN and LINEAR16 and _PRECISION != 1 and LINEAR16_MIN_ROWS <= R < LINEAR_SMALL_MAX_ROWS
-            and N % 8 == 0 and K % 8 == 0)
+    """The one-launch Linear of csrc/linear_small.hip: 128 <= rows < 2048."""
+    return LINEAR16 and _PRECISION != 1 and LINEAR16_MIN_ROWS <= R < LINEAR_SMALL_MAX_ROWS and N % 8 == 0 and K % 8 == 0
 
 
 def _lin16_ok(R, N, K):
@@ -382,7 +378,6 @@ def cvt_bf16(x2, want=True, wantT=False, ldt=None, colsum_out=None, act_aux=None
 
 _W16_TABLE = None      # (signature, device job table, njobs, total tiles) of the last batched refresh
 _W16_REFRESHED = -1    # epoch of the last batched refresh
-_W16_BATCH = True
 
 
 def _refresh_weights16():
@@ -449,7 +444,7 @@ def weight16(W, lo=False, f16=False):
     if ent is not None:
         owner = ent[0]()
         if owner is not None and _owns(owner, key[0]):
-            if _W16_BATCH and ent[2] != _W16_EPOCH and _W16_REFRESHED != _W16_EPOCH:
+            if ent[2] != _W16_EPOCH and _W16_REFRESHED != _W16_EPOCH:
                 _refresh_weights16()
                 ent = _W16.get(key, ent)
             if ent[1] == owner._version and ent[2] == _W16_EPOCH and (not lo or (ent[5] is not None and (ent[5].dtype == torch.float16) == f16)):
@@ -612,14 +607,15 @@ def mlp16_ok(R, K, Hd, N):
     return _lin16_ok(R, Hd, K) and _lin16_ok(R, N, Hd)
 
 
-# Weight gradients on ROW-MAJOR bf16 operands (spe_gemm_bf16tn: LDS transpose reads): no producer writes a transposed bf16
-# copy any more - not the activation conversions (x16T), not the backward conversions (dy16T), not the GEMM epilogues.
-DW_TN = True
+# Weight gradients run on ROW-MAJOR bf16 operands (spe_gemm_bf16tn: LDS transpose reads): a saved bf16 activation is always the
+# row-major copy, and no producer in this package asks for a transposed one - not the activation conversions, not the backward
+# conversions, not the GEMM epilogues.  The library entry points still offer the transposed outputs; their wrappers pass them through.
 
 
 def layerscale_residual_bwd16(dout2, y2, gamma, Rp, db_out=None, dg_out=None, want_rowmajor=True, want_T=True, drop=None, sscale=None, rps=1):
-    """Backward of out = x + gamma * y when y is the output of a Linear on the bf16-copy GEMMs: -> (dy16 [R,C], dy16T
-    [C,Rp], db [C], dgamma [C]); dy = gamma * dout exists only as those bf16 operands."""
+    """Backward of out = x + gamma * y when y is the output of a Linear on the bf16-copy GEMMs: -> (dy16 [R,C] or None, dy16T
+    [C,Rp] zero padded or None, db [C], dgamma [C]); dy = gamma * dout exists only as those bf16 copies.  The Linear nodes take the
+    row-major copy alone (want_T=False): it is the operand of both their dx and their dW product."""
     R, C = dout2.shape
     dev = dout2.device
     dy16 = torch.empty((R, C), device=dev, dtype=torch.bfloat16) if want_rowmajor else None
@@ -637,43 +633,34 @@ def layerscale_residual_bwd16(dout2, y2, gamma, Rp, db_out=None, dg_out=None, wa
 
 
 def linear_res_fwd(x2, W, b, res, gamma, save=True, src=None, drop=None, sscale=None, rps=1):
-    """out = res + gamma * (x2 @ W.T + b) on the bf16-copy GEMM with the residual in its epilogue.  -> (out, (x16T, y))."""
+    """out = res + gamma * (x2 @ W.T + b) on the bf16-copy GEMM with the residual in its epilogue.  -> (out, (x16, y))."""
     R, K = x2.shape
     N = W.shape[0]
     dev = x2.device
     sp = split_fwd()
-    x16, x16T, x16lo = act16(x2, save and not DW_TN, src, want_lo=sp)
+    x16, x16lo = act16(x2, src, want_lo=sp)
     out = torch.empty((R, N), device=dev, dtype=torch.float32)
     # the branch output y is kept for the LayerScale gamma gradient only (dgamma = sum dout * y): fp16, like the MLP's pre-activation
     y = torch.empty((R, N), device=dev, dtype=torch.float16 if MLP_PRE_F16 else torch.float32) if save else None
     Wt = weight16(W, lo=sp)
     gemm16_ex(x16, Wt[0], R, N, K, K, K, bias=b, C=out, C2=y, res=res, rgamma=gamma, Alo=x16lo, Blo=Wt[2] if sp else None,
               drop=drop, sscale=sscale, rps=rps)
-    return out, ((x16 if DW_TN else x16T), y)
+    return out, (x16, y)
 
 
 def linear_res_bwd(dout2, saved, W, gamma, need_dx=True, grad_bufs=(None, None, None), drop=None, sscale=None, rps=1, pre=None):
     """Backward of linear_res_fwd: (dx, dW, db, dgamma); gamma * dout only exists as the bf16 operands of the two GEMMs.
     pre = (dy16, db, dgamma): the LayerScale part was already taken by the LayerNorm backward that produced dout (layernorm_bwd ls=)."""
-    xs, y = saved
+    x16, y = saved
     R, N = dout2.shape
     K = W.shape[1]
     gW, gb, gg = grad_bufs
-    if _is_rowmajor_save(xs, R):
-        Rp = ((R + 63) // 64) * 64
-        if pre is not None:
-            dy16, db, dg = pre
-        else:
-            dy16, _, db, dg = layerscale_residual_bwd16(dout2, y, gamma, Rp, db_out=gb, dg_out=gg, want_rowmajor=True, want_T=False,
-                                                        drop=drop, sscale=sscale, rps=rps)
-        dW = _dw16_tn(dy16, xs, N, K, R, gW)
+    if pre is not None:         # the sums are already in db / dgamma: running the LayerScale backward again would count them twice
+        dy16, db, dg = pre
     else:
-        if pre is not None:         # the sums are already in db / dgamma: running the LayerScale backward again would count them twice
-            raise RuntimeError("spe_amd.kernels.linear_res_bwd: a LayerNorm backward took this node's LayerScale part, but its save is not row-major")
-        Rp = xs.shape[1]
-        dy16, dy16T, db, dg = layerscale_residual_bwd16(dout2, y, gamma, Rp, db_out=gb, dg_out=gg, want_rowmajor=need_dx,
-                                                        drop=drop, sscale=sscale, rps=rps)
-        dW = _dw16(dy16T, xs, N, K, Rp, gW)
+        dy16, _, db, dg = layerscale_residual_bwd16(dout2, y, gamma, ((R + 63) // 64) * 64, db_out=gb, dg_out=gg, want_rowmajor=True, want_T=False,
+                                                    drop=drop, sscale=sscale, rps=rps)
+    dW = _dw16_tn(dy16, x16, N, K, R, gW)
     dx = None
     if need_dx:
         dx = torch.empty((R, K), device=dout2.device, dtype=torch.float32)
@@ -705,16 +692,17 @@ def mlp_f16_ok(R, K, Hd, N):
 
 def mlp_gelu_fwd(x2, W1, b1, W2, b2, res=None, gamma=None, save=True, src=None, drop1=None, drop2=None, sscale=None, rps=1):
     """y = fc2(gelu(fc1(x2))) with every intermediate that the next GEMM needs emitted as bf16 by the producing GEMM's
-    epilogue: fc1 writes the fp32 pre-activation (for the backward) and the bf16 activation h16 / h16T, never the fp32
-    activation.  -> (y [R,N] fp32, saved = (x16T, pre, h16T))."""
+    epilogue: fc1 writes the pre-activation (for the backward: fp32, or fp16 under MLP_PRE_F16) and the row-major bf16 activation
+    h16, never the fp32 activation.  -> (y [R,N] fp32, saved = (x16, pre, h16)); with res / gamma (out = res + gamma * y in the fc2
+    epilogue) -> (out, saved = (x16, pre, h16, y))."""
     R, K = x2.shape
     Hd, N = W1.shape[0], W2.shape[0]
     dev = x2.device
     # save = False (no gradient wanted: inference): none of the tensors that only the backward reads is produced
     sp = split_fwd()                         # bf16s forward: both products on (hi, lo) operand pairs, fc1 emits gelu(pre) as a pair
-    if res is not None and DW_TN and mlp_f16_ok(R, K, Hd, N):
+    if res is not None and mlp_f16_ok(R, K, Hd, N):
         # ... or on single-term fp16 operands: x as (bf16 for the backward, fp16), fc1 emits gelu(pre) as (bf16 for the backward, fp16 for fc2)
-        x16, _, xh = act16(x2, False, src, want_lo=True, lo_f16=True)
+        x16, xh = act16(x2, src, want_lo=True, lo_f16=True)
         pre = torch.empty((R, Hd), device=dev, dtype=torch.float16 if MLP_PRE_F16 else torch.float32) if save else None
         h16 = torch.empty((R, Hd), device=dev, dtype=torch.bfloat16)
         hh = torch.empty((R, Hd), device=dev, dtype=torch.float16)
@@ -724,97 +712,77 @@ def mlp_gelu_fwd(x2, W1, b1, W2, b2, res=None, gamma=None, save=True, src=None, 
         y = torch.empty((R, N), device=dev, dtype=torch.float16 if MLP_PRE_F16 else torch.float32) if save else None
         gemm16_ex(hh, W2h, R, N, Hd, Hd, Hd, bias=b2, C=out, C2=y, res=res, rgamma=gamma, drop=drop2, sscale=sscale, rps=rps, op_f16=True)
         return out, (x16, pre, h16, y)
-    x16, x16T, x16lo = act16(x2, save and not DW_TN, src, want_lo=sp)
-    Rp = ((R + 63) // 64) * 64
+    x16, x16lo = act16(x2, src, want_lo=sp)
     # the pre-activation is kept for gelu'(.) of the backward only: fp16 (11 significant bits: the derivative is exact to ~3e-4,
     # an order below the bf16 operand rounding of the backward products) - half the bytes of the largest activation of the block
     pre = torch.empty((R, Hd), device=dev, dtype=torch.float16 if MLP_PRE_F16 else torch.float32) if save else None
     h16 = torch.empty((R, Hd), device=dev, dtype=torch.bfloat16)
     h16lo = torch.empty((R, Hd), device=dev, dtype=torch.bfloat16) if sp else None
-    h16T = torch.empty((Hd, Rp), device=dev, dtype=torch.bfloat16) if (save and not DW_TN) else None
     W1t, W2t = weight16(W1, lo=sp), weight16(W2, lo=sp)
     W1lo, W2lo = (W1t[2], W2t[2]) if sp else (None, None)
     # drop1 = (p, seed, offset): timm Mlp's dropout after the activation - h16 then holds dropout(gelu(pre))
-    gemm16_ex(x16, W1t[0], R, Hd, K, K, K, bias=b1, C2=pre, out16=h16, out16T=h16T, act=2, Alo=x16lo, Blo=W1lo, out16lo=h16lo, drop=drop1)
+    gemm16_ex(x16, W1t[0], R, Hd, K, K, K, bias=b1, C2=pre, out16=h16, act=2, Alo=x16lo, Blo=W1lo, out16lo=h16lo, drop=drop1)
     y = torch.empty((R, N), device=dev, dtype=torch.float32)
-    if DW_TN:
-        x16T, h16T = x16, h16            # what the backward gets: the row-major copies
     if res is None:
         gemm16(h16, W2t[0], y, R, N, Hd, Hd, Hd, N, bias=b2, Alo=h16lo, Blo=W2lo)
-        return y, (x16T, pre, h16T)
+        return y, (x16, pre, h16)
     # LayerScale residual in the fc2 epilogue: out = res + gamma * y ; y is kept for the gamma gradient
     out = torch.empty((R, N), device=dev, dtype=torch.float32)
     if MLP_PRE_F16:
         y = torch.empty((R, N), device=dev, dtype=torch.float16)        # kept for the gamma gradient only
     gemm16_ex(h16, W2t[0], R, N, Hd, Hd, Hd, bias=b2, C=out, C2=y if save else None, res=res, rgamma=gamma, Alo=h16lo, Blo=W2lo,
               drop=drop2, sscale=sscale, rps=rps)
-    return out, (x16T, pre, h16T, y)
+    return out, (x16, pre, h16, y)
 
 
-def _dw16(dy16T, x16T, N, K, Rp, dW_out):
-    """dW [N,K] = dy16T [N,Rp] @ x16T[K,Rp]^T, split-K slabs summed into dW_out (zeroed bucket view) when given."""
-    dev = dy16T.device
-    sk = min(auto_splitk(N, K, Rp, 1), Rp // 64)
+def _dw_slabs(launch, sk, N, K, dW_out, dev):
+    """A weight gradient dW [N,K] whose contraction over the rows is split `sk` ways: launch(C, splitk) runs the product into C -
+    private slabs [sk, N*K] (splitk = -sk) that one column-sum launch adds up into dW_out (the parameter's bucket view: overwritten,
+    so it needs no zeroing) or a fresh tensor; sk <= 1: straight into the destination."""
     if sk > 1:
         ws = torch.empty((sk, N * K), device=dev, dtype=torch.float32)
-        gemm16(dy16T, x16T, ws, N, K, Rp, Rp, Rp, K, splitk=-sk)
+        launch(ws, -sk)
         return colsum(ws, out=None if dW_out is None else dW_out.view(-1), accumulate=dW_out is None).view(N, K)
     dW = dW_out if dW_out is not None else torch.empty((N, K), device=dev, dtype=torch.float32)
-    gemm16(dy16T, x16T, dW, N, K, Rp, Rp, Rp, K)
+    launch(dW, 1)
     return dW
-
-
-def _is_rowmajor_save(xs, R):
-    """Saved bf16 activations are row-major [R, K] (DW_TN, fixed for the life of the process) or the padded transpose [K, Rp]."""
-    return DW_TN and xs.dtype == torch.bfloat16
 
 
 def _dw16_tn(dy16, x16, N, K, R, dW_out, lda=None):
     """dW [N,K] = dy16 [R,N]^T @ x16 [R,K] on row-major operands; split over the rows into slabs summed into dW_out.
     lda: row stride of dy16 when it is a column block of a wider matrix."""
-    dev = dy16.device
     lda = N if lda is None else lda
     sk = min(auto_splitk(N, K, R, 1), max(1, R // 64))
-    if sk > 1:
-        ws = torch.empty((sk, N * K), device=dev, dtype=torch.float32)
-        gemm16_tn(dy16, x16, ws, N, K, R, lda, K, K, splitk=-sk)
-        return colsum(ws, out=None if dW_out is None else dW_out.view(-1), accumulate=dW_out is None).view(N, K)
-    dW = dW_out if dW_out is not None else torch.empty((N, K), device=dev, dtype=torch.float32)
-    gemm16_tn(dy16, x16, dW, N, K, R, lda, K, K)
-    return dW
+    return _dw_slabs(lambda C, splitk: gemm16_tn(dy16, x16, C, N, K, R, lda, K, K, splitk=splitk), sk, N, K, dW_out, dy16.device)
 
 
 def mlp_gelu_bwd(dy2, saved, W1, W2, need_dx=True, grad_bufs=(None, None, None, None), gamma=None, dg_out=None,
                  drop1=None, drop2=None, sscale=None, rps=1, ls_pre=None):
     """Backward of mlp_gelu_fwd.  dy2 [R,N] fp32.  -> (dx, dW1, db1, dW2, db2).  The gradient w.r.t. the pre-activation
-    exists only as the bf16 copies (row-major for dx, transposed for dW1) written by the dh GEMM's epilogue, which also
-    applies gelu' and accumulates db1.  grad_bufs: zeroed bucket views for (dW1, db1, dW2, db2) or None."""
-    x16T, pre, h16T = saved[:3]
+    exists only as the row-major bf16 copy dp16 (the operand of both dx and dW1) written by the dh GEMM's epilogue, which also
+    applies gelu' and accumulates db1.  grad_bufs: bucket views for (dW1, db1, dW2, db2) or None."""
+    x16, pre, h16 = saved[:3]
     R, N = dy2.shape
     Hd, K = W1.shape
-    tn = _is_rowmajor_save(x16T, R)
-    Rp = ((R + 63) // 64) * 64 if tn else x16T.shape[1]
     dev = dy2.device
     gW1, gb1, gW2, gb2 = grad_bufs
     dg = None
-    if ls_pre is not None and (gamma is None or not tn):      # never fall through: the LayerNorm backward already added this node's sums
+    if ls_pre is not None and gamma is None:      # never fall through: the LayerNorm backward already added this node's sums
         raise RuntimeError("spe_amd.kernels.mlp_gelu_bwd: a LayerNorm backward took this node's LayerScale part, but the node cannot consume it")
-    if gamma is not None and ls_pre is not None and tn:      # the LayerScale part came with the LayerNorm backward that produced dy2 (layernorm_bwd ls=)
+    if ls_pre is not None:         # the LayerScale part came with the LayerNorm backward that produced dy2 (layernorm_bwd ls=)
         dy16, db2, dg = ls_pre
-        dy16T = None
     elif gamma is not None:        # residual form: dy2 is d(out); the branch gradient gamma * dout only exists in bf16
-        dy16, dy16T, db2, dg = layerscale_residual_bwd16(dy2, saved[3], gamma, Rp, db_out=gb2, dg_out=dg_out, want_T=not tn,
-                                                         drop=drop2, sscale=sscale, rps=rps)
+        dy16, _, db2, dg = layerscale_residual_bwd16(dy2, saved[3], gamma, ((R + 63) // 64) * 64, db_out=gb2, dg_out=dg_out, want_T=False,
+                                                     drop=drop2, sscale=sscale, rps=rps)
     else:
         db2 = _zeros_or(gb2, N, dev)
-        dy16, dy16T = cvt_bf16(dy2, True, not tn, ldt=Rp, colsum_out=db2)
-    dW2 = _dw16_tn(dy16, h16T, N, Hd, R, gW2) if tn else _dw16(dy16T, h16T, N, Hd, Rp, gW2)
+        dy16, _ = cvt_bf16(dy2, True, False, colsum_out=db2)
+    dW2 = _dw16_tn(dy16, h16, N, Hd, R, gW2)
     # dpre = (dy @ W2) * gelu'(pre): bf16 only
     db1 = _zeros_or(gb1, Hd, dev)
-    dp16 = torch.empty((R, Hd), device=dev, dtype=torch.bfloat16) if (need_dx or tn) else None
-    dp16T = torch.empty((Hd, Rp), device=dev, dtype=torch.bfloat16) if not tn else None
-    gemm16_ex(dy16, weight16(W2)[1], R, Hd, N, N, N, out16=dp16, out16T=dp16T, colsum=db1, aux=pre, act=2, drop=drop1)      # ... times the mask of drop1
-    dW1 = _dw16_tn(dp16, x16T, Hd, K, R, gW1) if tn else _dw16(dp16T, x16T, Hd, K, Rp, gW1)
+    dp16 = torch.empty((R, Hd), device=dev, dtype=torch.bfloat16)
+    gemm16_ex(dy16, weight16(W2)[1], R, Hd, N, N, N, out16=dp16, colsum=db1, aux=pre, act=2, drop=drop1)      # ... times the mask of drop1
+    dW1 = _dw16_tn(dp16, x16, Hd, K, R, gW1)
     dx = None
     if need_dx:
         dx = torch.empty((R, K), device=dev, dtype=torch.float32)
@@ -824,28 +792,28 @@ def mlp_gelu_bwd(dy2, saved, W1, W2, need_dx=True, grad_bufs=(None, None, None, 
     return dx, dW1, db1, dW2, db2
 
 
-def act16(x2, wantT, src=None, want_lo=False, lo_f16=False):
-    """bf16 copies (row-major, transposed when wantT, and the low part of the split operand when want_lo) of an activation
-    [R,K] -> (x16, x16T, x16lo).  `src`: the tensor object the caller holds (x2 is a reshape of it) - the copies are
-    remembered ON that object (attribute, checked against its version counter), so an activation that feeds several Linears
-    (the decoder's memory, positional embedding, tgt, query_pos; q / k / v of the class attention) is converted once; they die
-    with the tensor."""
+def act16(x2, src=None, want_lo=False, lo_f16=False):
+    """Row-major bf16 copy (and the low part of the split operand when want_lo) of an activation [R,K] -> (x16, x16lo).
+    `src`: the tensor object the caller holds (x2 is a reshape of it) - the copies are remembered ON that object (attribute
+    _spe16 = (version, x16, None, x16lo): see attach16; checked against its version counter), so an activation that feeds several
+    Linears (the decoder's memory, positional embedding, tgt, query_pos; q / k / v of the class attention) is converted once; they
+    die with the tensor."""
     if src is not None:
         ent = getattr(src, "_spe16", None)
-        if (ent is not None and ent[0] == src._version and ent[1].shape == x2.shape and (ent[2] is not None or not wantT)
+        if (ent is not None and ent[0] == src._version and ent[1].shape == x2.shape
                 and (not want_lo or (ent[3] is not None and (ent[3].dtype == torch.float16) == lo_f16))):
-            return ent[1], ent[2], (ent[3] if want_lo else None)
+            return ent[1], (ent[3] if want_lo else None)
     # lo_f16: the second copy is IEEE fp16(x) - the operand of a single-term fp16 product - instead of the low part of the split
     x16lo = torch.empty(x2.shape, device=x2.device, dtype=torch.float16 if lo_f16 else torch.bfloat16) if want_lo else None
-    x16, x16T = cvt_bf16(x2, True, wantT, out_lo=x16lo, lo_f16=lo_f16 and want_lo)
+    x16, _ = cvt_bf16(x2, True, False, out_lo=x16lo, lo_f16=lo_f16 and want_lo)
     if src is not None:
-        src._spe16 = (src._version, x16, x16T, x16lo)
-    return x16, x16T, x16lo
+        attach16(src, x16, x16lo)
+    return x16, x16lo
 
 
 def linear_fwd(x2, W, b, act=0, want_pre=False, save_for_dw=True, src=None):
     """y = act(x2 @ W.T + b); x2 [R,K] contiguous, W [N,K].  -> (y, pre-activation or None, xsave): xsave is what
-    linear_bwd needs of x - x2 itself, or on the bf16 path the padded bf16 transpose x16T [K, Rp]."""
+    linear_bwd needs of x - x2 itself, or on the bf16 paths (when save_for_dw) its row-major bf16 copy x16 [R, K]."""
     _chk(x2, W, b)
     R, K = x2.shape
     N = W.shape[0]
@@ -862,27 +830,24 @@ def linear_fwd(x2, W, b, act=0, want_pre=False, save_for_dw=True, src=None):
         if x16 is None and save_for_dw:
             x16 = x16_out = torch.empty((R, K), device=x2.device, dtype=torch.bfloat16)
             if src is not None:
-                src._spe16 = (src._version, x16, None, None)
+                attach16(src, x16)
         _call("spe_linear_small_fwd", _p(x2), x2.stride(0), _p(Wt[0]), _p(Wt[2] if sp else None), _p(b), _p(y), _p(pre), _p(x16_out),
               R, N, K, N, int(act), _st())
         return y, pre, (x16 if save_for_dw else x2)
     if _lin16_ok(R, N, K) and W.is_contiguous():
         sp = split_fwd()
-        x16, x16T, x16lo = act16(x2, save_for_dw and not DW_TN, src, want_lo=sp)
+        x16, x16lo = act16(x2, src, want_lo=sp)
         Wt = weight16(W, lo=sp)
         gemm16(x16, Wt[0], y, R, N, K, K, K, N, bias=b, C2=pre, act=act, Alo=x16lo, Blo=Wt[2] if sp else None)
-        return y, pre, ((x16 if DW_TN else x16T) if save_for_dw else x2)
+        return y, pre, (x16 if save_for_dw else x2)
     gemm(x2, W, y, R, N, K, K, K, N, False, True, bias=b, C2=pre, act=act)
     return y, pre, x2
-
-
-LINEAR_GROUP = True
 
 
 def linear_group_ok(R, Ws, bs):
     """Several Linears of one shape on one input of a few hundred rows: the one-launch group form of csrc/linear_small.hip."""
     N, K = Ws[0].shape
-    return (LINEAR_GROUP and 2 <= len(Ws) <= 16 and _lin_small_ok(R, N, K) and N % 128 == 0
+    return (2 <= len(Ws) <= 16 and _lin_small_ok(R, N, K) and N % 128 == 0
             and all(W.shape == Ws[0].shape and W.is_contiguous() for W in Ws) and all(b is not None for b in bs))
 
 
@@ -904,7 +869,7 @@ def linear_group_fwd(x2, Ws, bs, src=None, adds=None):
     if x16 is None:
         x16 = x16_out = torch.empty((R, K), device=x2.device, dtype=torch.bfloat16)
         if src is not None:
-            src._spe16 = (src._version, x16, None, None)
+            attach16(src, x16)
     ys = [torch.empty((R, N), device=x2.device, dtype=torch.float32) for _ in Ws]
     _call("spe_linear_small_group_fwd", _p(x2), x2.stride(0), _ptr_array([t_[0].data_ptr() for t_ in trip]),
           _ptr_array([t_[2].data_ptr() for t_ in trip]) if sp else None, _ptr_array([b.data_ptr() for b in bs]),
@@ -944,7 +909,7 @@ def linear_bwd(dy2, xsave, W, need_dx=True, need_dw=True, need_db=True, dW_out=N
     K = W.shape[1]
     dx = dW = db = None
     x16 = xsave.dtype == torch.bfloat16
-    if (x16 or not need_dw) and _lin_small_ok(R, N, K) and W.is_contiguous() and (not x16 or _is_rowmajor_save(xsave, R)):
+    if (x16 or not need_dw) and _lin_small_ok(R, N, K) and W.is_contiguous():
         # one launch: dx, dW and db (csrc/linear_small.hip); dW / db are overwritten, so the bucket views need no zeroing
         dev = dy2.device
         if need_dx:
@@ -957,27 +922,15 @@ def linear_bwd(dy2, xsave, W, need_dx=True, need_dw=True, need_db=True, dW_out=N
               _p(weight16(W)[1] if need_dx else None), _p(dx), _p(dW), _p(db), R, N, K, _st())
         return dx, dW, db
     if (x16 or not need_dw) and _lin16_ok(R, N, K) and W.is_contiguous():
-        tn = x16 and _is_rowmajor_save(xsave, R)
-        Rp = None if (tn or not x16) else xsave.shape[1]
         if need_db:                     # the bias gradient rides on the conversion pass over dy
             db = _zeros_or(db_out, N, dy2.device)
-        dy16, dy16T = cvt_bf16(dy2, need_dx or (need_dw and tn), need_dw and x16 and not tn, ldt=Rp, colsum_out=db,
-                               act_aux=act_aux if act else None, act=act)
+        dy16, _ = cvt_bf16(dy2, need_dx or need_dw, False, colsum_out=db, act_aux=act_aux if act else None, act=act)
         need_db = False
         if need_dx:
             dx = torch.empty((R, K), device=dy2.device, dtype=torch.float32)
             gemm16(dy16, weight16(W)[1], dx, R, K, N, N, N, K)
-        if need_dw and tn:
+        if need_dw:                     # (only with a bf16 save: see the test above)
             dW = _dw16_tn(dy16, xsave, N, K, R, dW_out)
-        elif need_dw:
-            sk = min(auto_splitk(N, K, R, 1), Rp // 64)
-            if sk > 1:
-                ws = torch.empty((sk, N * K), device=dy2.device, dtype=torch.float32)
-                gemm16(dy16T, xsave, ws, N, K, Rp, Rp, Rp, K, splitk=-sk)
-                dW = colsum(ws, out=None if dW_out is None else dW_out.view(-1), accumulate=dW_out is None).view(N, K)
-            else:
-                dW = dW_out if dW_out is not None else torch.empty((N, K), device=dy2.device, dtype=torch.float32)
-                gemm16(dy16T, xsave, dW, N, K, Rp, Rp, Rp, K)
     else:
         if x16:
             raise RuntimeError("linear_bwd: bf16 activations were saved but the bf16 GEMM path is disabled now")
@@ -988,14 +941,9 @@ def linear_bwd(dy2, xsave, W, need_dx=True, need_dw=True, need_db=True, dW_out=N
             dx = torch.empty((R, K), device=dy2.device, dtype=torch.float32)
             gemm(dy2, W, dx, R, K, N, N, K, K, False, False)
         if need_dw:
-            sk = auto_splitk(N, K, R, 1)
-            if sk > 1:       # slab split-K: no atomics; the slabs are summed by one column-sum launch
-                ws = torch.empty((sk, N * K), device=dy2.device, dtype=torch.float32)
-                gemm(dy2, x2, ws, N, K, R, N, K, K, True, False, splitk=-sk)
-                dW = colsum(ws, out=None if dW_out is None else dW_out.view(-1), accumulate=dW_out is None).view(N, K)
-            else:
-                dW = dW_out if dW_out is not None else torch.empty((N, K), device=dy2.device, dtype=torch.float32)
-                gemm(dy2, x2, dW, N, K, R, N, K, K, True, False)
+            # slab split-K: no atomics; the slabs are summed by one column-sum launch
+            dW = _dw_slabs(lambda C, splitk: gemm(dy2, x2, C, N, K, R, N, K, K, True, False, splitk=splitk), auto_splitk(N, K, R, 1), N, K,
+                           dW_out, dy2.device)
     if need_db:
         db = _zeros_or(db_out, N, dy2.device)
         _call("spe_colsum", _p(dy2), _p(db), R, N, N, 1, _st())
@@ -1039,8 +987,8 @@ def layernorm_fwd(x2, g, b, eps, want16=False, f16=False):
 
 def produces16(R, C):
     """A producer of a [R, C] activation should also emit its bf16 copy: the consumer Linear takes the bf16-copy GEMM path and
-    needs no transposed copy (DW_TN)."""
-    return DW_TN and LINEAR16 and _PRECISION != 1 and R >= LINEAR16_MIN_ROWS and C % 8 == 0
+    needs nothing else of it (the row-major copy is the operand of its weight gradient too)."""
+    return LINEAR16 and _PRECISION != 1 and R >= LINEAR16_MIN_ROWS and C % 8 == 0
 
 
 def attach16(t, x16, x16lo=None):

@@ -20,9 +20,6 @@ from .attention import MultiheadAttention
 from .layers import MLP, Dropout, LayerNorm, Linear
 
 
-MEMSIDE_BATCH = True
-
-
 def gen_sineembed_for_position(pos_tensor, d_model=256):
     """[.., 2] normalised (x, y) -> [.., d_model] sine embedding.  The exponent divisor is the
     reference's hard-coded 128 (transformer.py:41), NOT d_model/2.  Tiny [B,Q,d] tensor ops."""
@@ -206,7 +203,7 @@ class TransformerDecoder(nn.Module):
         pos_w = [layer.ca_kpos_proj for layer in self.layers]
         Wm, bm = [m.weight for m in mem_w], [m.bias for m in mem_w]
         Wp, bp = [m.weight for m in pos_w], [m.bias for m in pos_w]
-        if not (MEMSIDE_BATCH and memory.is_cuda and ops.multi_linear_ok(memory, Wm, bm) and ops.multi_linear_ok(pos, Wp, bp)):
+        if not (memory.is_cuda and ops.multi_linear_ok(memory, Wm, bm) and ops.multi_linear_ok(pos, Wp, bp)):
             return
         B, S, d = memory.shape
         H, dh = self.layers[0].nhead, d // self.layers[0].nhead

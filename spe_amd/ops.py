@@ -78,7 +78,7 @@ class _MultiLinear(Function):
         sp = K.split_fwd()                    # bf16s forward: (hi, lo) operand pairs
         cat = K.weightcat16(Ws, bs, lo=sp)
         Wc, WcT, bc = cat[:3]
-        x16, _, x16lo = K.act16(x2, False, x, want_lo=sp)
+        x16, x16lo = K.act16(x2, x, want_lo=sp)
         y = torch.empty((R, n * N), device=x.device, dtype=torch.float32)
         K.gemm16(x16, Wc, y, R, n * N, Kd, Kd, Kd, n * N, bias=bc, Alo=x16lo, Blo=cat[3] if sp else None)
         ctx.params = (Ws, bs)
@@ -120,7 +120,7 @@ class _MultiLinear(Function):
 def multi_linear_ok(x, Ws, bs):
     R = x.numel() // x.shape[-1]
     N, Kd = Ws[0].shape
-    return (K.DW_TN and K._lin16_ok(R, len(Ws) * N, Kd) and all(W.shape == Ws[0].shape and W.is_contiguous() for W in Ws)
+    return (K._lin16_ok(R, len(Ws) * N, Kd) and all(W.shape == Ws[0].shape and W.is_contiguous() for W in Ws)
             and all(b is not None for b in bs) and N % 8 == 0)
 
 
@@ -612,16 +612,13 @@ class _QkvTalkingAttention(Function):
         return dx, dW, db.view_as(bq), dWl, dbl, dWw, dbw, None, None, None, None
 
 
-QKV_FUSED = True        # module attribute, not an environment knob
-
-
 def qkv_talking_attention_ok(x, Wq, bq, num_heads):
-    """The one-node form needs the bf16-operand Linear path with row-major saves, a bias, the fused attention kernels and gradients."""
+    """The one-node form needs the bf16-operand Linear path, a bias, the fused attention kernels and gradients."""
     C = x.shape[-1]
     R = x.numel() // C
-    return (QKV_FUSED and x.is_cuda and bq is not None and Wq.is_contiguous() and torch.is_grad_enabled()
+    return (x.is_cuda and bq is not None and Wq.is_contiguous() and torch.is_grad_enabled()
             and (x.requires_grad or Wq.requires_grad) and Wq.requires_grad and bq.requires_grad
-            and K.get_precision() != "bf16x3" and K.DW_TN and K._lin16_ok(R, Wq.shape[0], C) and not K._lin_small_ok(R, Wq.shape[0], C)
+            and K.get_precision() != "bf16x3" and K._lin16_ok(R, Wq.shape[0], C) and not K._lin_small_ok(R, Wq.shape[0], C)
             and K.fused_supported(num_heads, C // num_heads))
 
 
@@ -632,7 +629,7 @@ def qkv_talking_attention(x, Wq, bq, Wl, bl, Ww, bw, num_heads, scale, p_drop=0.
 class _MlpGelu(Function):
     """fc2(gelu(fc1(x))) of the backbone block (reference models/cait.py:405-412: timm Mlp with drop = 0) as ONE autograd
     node on the bf16-copy GEMMs: the activation and the gradient w.r.t. the pre-activation never exist in fp32 - the
-    producing GEMM epilogues write the bf16 (and transposed bf16) operands of the following GEMMs and the bias gradient."""
+    producing GEMM epilogues write the row-major bf16 operands of the following GEMMs and the bias gradient."""
 
     @staticmethod
     @K.forward_scope
@@ -651,16 +648,13 @@ class _MlpGelu(Function):
     @staticmethod
     @K.backward_scope
     def backward(ctx, dy):
-        x16T, pre, h16T, W1, W2 = ctx.saved_tensors
+        x16, pre, h16, W1, W2 = ctx.saved_tensors
         dy2 = dy.reshape(-1, W2.shape[0])
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
         bufs = tuple(K.grad_buffer(p) for p in ctx.params)
-        dx, dW1, db1, dW2, db2 = K.mlp_gelu_bwd(dy2, (x16T, pre, h16T), W1, W2, ctx.needs_input_grad[0], bufs)
+        dx, dW1, db1, dW2, db2 = K.mlp_gelu_bwd(dy2, (x16, pre, h16), W1, W2, ctx.needs_input_grad[0], bufs)
         return (dx.view(*dy.shape[:-1], W1.shape[1]) if dx is not None else None), dW1, db1, dW2, db2
-
-
-FUSE_LINEAR_RES = True
 
 
 class _LinearRes(Function):
@@ -685,7 +679,7 @@ class _LinearRes(Function):
         ctx.drop = (float(p_drop), *K.next_rng()) if p_drop > 0 else None
         # `single`: the caller promises that the output feeds one LayerNorm-skip node and nothing else - that norm's backward may then take this
         # node's LayerScale backward along (ops._LayerNormSkip); only without rates, with fp32 saves and bias / gamma gradients wanted
-        ctx.ls_single = bool(single and train and p_drop <= 0 and sscale is None and not K.MLP_PRE_F16 and K.DW_TN and W.requires_grad
+        ctx.ls_single = bool(single and train and p_drop <= 0 and sscale is None and not K.MLP_PRE_F16 and W.requires_grad
                              and b.requires_grad and gamma.requires_grad)
         ctx.ls_done = None
         ctx.rps = r2.shape[0] // xres.shape[0]
@@ -699,14 +693,14 @@ class _LinearRes(Function):
     @staticmethod
     @K.backward_scope
     def backward(ctx, dout):
-        x16T, y, W, gamma = ctx.saved_tensors[:4]
+        x16, y, W, gamma = ctx.saved_tensors[:4]
         ss = ctx.saved_tensors[4] if ctx.has_ss else None
         d2 = dout.reshape(-1, W.shape[0])
         if not d2.is_contiguous():
             d2 = d2.contiguous()
         pre = _ls_taken(ctx, dout if dout.is_contiguous() else d2)
         bufs = tuple(K.grad_buffer(p) for p in ctx.params)
-        dx, dW, db, dg = K.linear_res_bwd(d2, (x16T, y), W, gamma, ctx.needs_input_grad[0], bufs, drop=ctx.drop, sscale=ss, rps=ctx.rps, pre=pre)
+        dx, dW, db, dg = K.linear_res_bwd(d2, (x16, y), W, gamma, ctx.needs_input_grad[0], bufs, drop=ctx.drop, sscale=ss, rps=ctx.rps, pre=pre)
         return (dx.view(*dout.shape[:-1], W.shape[1]) if dx is not None else None), dW, db, dout, dg.view_as(gamma), None, None, None
 
 def _ls_args(prod):
@@ -740,7 +734,7 @@ def linear_residual(x, W, b, xres, gamma, sample_scale=None, p_drop=0.0, single=
     linear, dropout and layerscale_residual.  single: the result feeds ONE LayerNorm-skip node and nothing else (see _LinearRes)."""
     R = x.numel() // x.shape[-1]
     N, Kd = W.shape
-    if (FUSE_LINEAR_RES and (FUSE_DROP or (sample_scale is None and p_drop <= 0)) and b is not None and W.is_contiguous()
+    if ((FUSE_DROP or (sample_scale is None and p_drop <= 0)) and b is not None and W.is_contiguous()
             and gamma.is_contiguous() and N % 4 == 0 and N <= 1024 and K._lin16_ok(R, N, Kd)
             and (sample_scale is None or (sample_scale.is_contiguous() and R % xres.shape[0] == 0))):
         return _LinearRes.apply(x, W, b, xres, gamma, sample_scale, p_drop, single)
@@ -767,7 +761,7 @@ class _MlpGeluRes(Function):
         # sites draw their streams in that order, like the unfused composition
         ctx.drop1 = (float(p_drop), *K.next_rng()) if p_drop > 0 else None
         ctx.drop2 = (float(p_drop), *K.next_rng()) if p_drop > 0 else None
-        ctx.ls_single = bool(single and train and p_drop <= 0 and sscale is None and not K.MLP_PRE_F16 and K.DW_TN and W2.requires_grad
+        ctx.ls_single = bool(single and train and p_drop <= 0 and sscale is None and not K.MLP_PRE_F16 and W2.requires_grad
                              and b2.requires_grad and gamma.requires_grad)          # see _LinearRes
         ctx.ls_done = None
         ctx.rps = r2.shape[0] // xres.shape[0]
@@ -782,7 +776,7 @@ class _MlpGeluRes(Function):
     @staticmethod
     @K.backward_scope
     def backward(ctx, dout):
-        x16T, pre, h16T, y, W1, W2, gamma = ctx.saved_tensors[:7]
+        x16, pre, h16, y, W1, W2, gamma = ctx.saved_tensors[:7]
         ss = ctx.saved_tensors[7] if ctx.has_ss else None
         d2 = dout.reshape(-1, W2.shape[0])
         if not d2.is_contiguous():
@@ -790,7 +784,7 @@ class _MlpGeluRes(Function):
         W1p, b1p, W2p, b2p, gp = ctx.params
         taken = _ls_taken(ctx, dout if dout.is_contiguous() else d2)
         bufs = tuple(K.grad_buffer(p) for p in (W1p, b1p, W2p, b2p))
-        dx, dW1, db1, dW2, db2, dg = K.mlp_gelu_bwd(d2, (x16T, pre, h16T, y), W1, W2, ctx.needs_input_grad[0], bufs,
+        dx, dW1, db1, dW2, db2, dg = K.mlp_gelu_bwd(d2, (x16, pre, h16, y), W1, W2, ctx.needs_input_grad[0], bufs,
                                                      gamma=gamma, dg_out=K.grad_buffer(gp), drop1=ctx.drop1, drop2=ctx.drop2,
                                                      sscale=ss, rps=ctx.rps, ls_pre=taken)
         return ((dx.view(*dout.shape[:-1], W1.shape[1]) if dx is not None else None), dW1, db1, dW2, db2, dout,
@@ -824,7 +818,8 @@ def mlp_gelu(x, W1, b1, W2, b2):
 
 def talking_heads_attention(qkv, Wl, bl, Ww, bw, num_heads, scale, p_drop=0.0, fused=None, acc=None):
     """fused=None: use the fused kernels in the bf16 / bf16s modes when the head geometry is supported (their forward runs
-    on fp16 operands in both modes, csrc/attn_fused.hip); the 3-term (bf16x3) parity mode keeps the fp32 materialised path.
+    on fp16 operands in both modes, csrc/attn_stats.hip and csrc/attn_flash.hip); the 3-term (bf16x3) parity mode keeps the
+    fp32 materialised path.
     acc: None, or (M, alpha) - M [B,N,N] fp32 += alpha * sum over heads of this block's softmax(proj_l(scale q k^T)) (taken before proj_w and
     dropout: reference models/cait.py:384, the map the woct0head backbone averages over heads and blocks for cams_cls_patch).  No gradient."""
     dh = qkv.shape[-1] // (3 * num_heads)
@@ -1023,8 +1018,8 @@ class _MemorySideKV(Function):
         if any(ctx.needs_input_grad):
             # the backward runs on single bf16 operands like every other Linear backward: bf16 copies of the inputs (shared with the
             # other consumers of `memory` / `pos`) and the transposed bf16 weight stack for the input gradient
-            m16, _, _ = K.act16(m2, False, memory)
-            p16, _, _ = K.act16(p2, False, pos)
+            m16, _ = K.act16(m2, memory)
+            p16, _ = K.act16(p2, pos)
             ctx.save_for_backward(m16, p16, K.weightcat16(Wm, bm)[1])
         toks = tuple(torch.zeros((1,), device=memory.device, dtype=torch.float32) for _ in range(L))
         return toks

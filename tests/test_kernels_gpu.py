@@ -553,7 +553,7 @@ def test_fused_mlp_matches_two_linears(dev):
     g0 = torch.autograd.grad(y0, (x, W1, b1, W2, b2), go)
     old = K.MLP_PRE_F16
     try:
-        # pre-activation saved in fp32: the same arithmetic as the two-node path; saved in fp16 (the default): gelu'(.) is taken of a
+        # pre-activation saved in fp32: the same arithmetic as the two-node path; saved in fp16 (MLP_PRE_F16; the default is fp32): gelu'(.) is taken of a
         # value rounded to 11 bits - the gradients through it move by < 1e-3, an order below their bf16 operand rounding
         for pre16, tol in ((False, 2e-6), (True, 1e-3)):
             K.MLP_PRE_F16 = pre16
@@ -616,7 +616,7 @@ def test_fused_mlp_residual_matches_composite(dev):
         assert rel(out, ref) < 1e-6
         for a, b, nm in zip(gr, g0, ["xn", "xres", "W1", "b1", "W2", "b2", "gamma"]):
             assert rel(a, b) < 5e-6, (nm, rel(a, b))
-        # the default: pre-activation and branch output saved as fp16 (they only enter gelu'(.) and the gamma gradient) - same
+        # MLP_PRE_F16 (off by default): pre-activation and branch output saved as fp16 (they only enter gelu'(.) and the gamma gradient) - same
         # output bit for bit, gradients within 1e-3 of the fp32-save ones
         K.MLP_PRE_F16 = True
         out16 = ops.mlp_gelu_residual(xn, W1, b1, W2, b2, xr, gamma)
