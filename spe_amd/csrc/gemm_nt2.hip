@@ -211,7 +211,10 @@ static int launch_nt2(const Gemm16Args& p, hipStream_t stream) {
 int spe_nt2_dispatch(const Gemm16Args& p, bool ex, hipStream_t stream) {
     static const int enabled = SPE_KNOB("SPE_GEMM_NT2", 1);      // developer knob (A/B against gemm_bf16.hip)
     const bool split = p.Alo != nullptr;
-    if (!enabled || p.M < 2048 || p.splitk != 1 || p.out16T || (p.K % 64) != 0 || p.K < 128 || p.N < 64) return SPE_NT2_NA;
+    // fp16 operands have no other kernel family, so their domain reaches down to ONE stage (K = 64: issue() clamps the refill to the
+    // last tile); the bf16 products of a contraction that short are faster on gemm_bf16.hip's kernels
+    const int kmin = (p.h16 & 1) ? 64 : 128;
+    if (!enabled || p.M < 2048 || p.splitk != 1 || p.out16T || (p.K % 64) != 0 || p.K < kmin || p.N < 64) return SPE_NT2_NA;
     if (!(p.h16 & 1) && (p.h16 & 4)) return -2;        // the fp16 second copy comes with fp16 operands only
     if ((p.h16 & 1) && ex) {
         // fp16 single-term operands with the extended epilogue (round 5: the backbone MLP's forward products in precision mode bf16s -

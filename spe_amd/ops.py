@@ -1002,8 +1002,10 @@ class _MemorySideKV(Function):
         m2 = m2 if m2.is_contiguous() else m2.contiguous()
         p2 = p2 if p2.is_contiguous() else p2.contiguous()
         # the bf16 backward fragments follow whether ANY backward can happen (holder.want_bwd: grad mode at the call site): with the memory-side
-        # projections frozen and the query side trainable, the cross-attention nodes still need K16 / Vf for dq
-        train = any(ctx.needs_input_grad) or bool(getattr(holder, "want_bwd", False))
+        # projections frozen and the query side trainable, the cross-attention nodes still need K16 / Vf for dq.  Under no_grad nothing
+        # can: needs_input_grad still reports the parameters' requires_grad there, so it must not decide alone
+        grad_mode = bool(getattr(holder, "want_bwd", True))
+        train = grad_mode
         Wmh, bmc = K.weightcat_f16(Wm, bm)
         Wph, bpc = K.weightcat_f16(Wp, bp)
         ym = torch.empty((B * S, 2 * L * d), device=memory.device, dtype=torch.float16)
@@ -1015,7 +1017,7 @@ class _MemorySideKV(Function):
         holder.ztok = torch.zeros((1,), device=memory.device, dtype=torch.float32)
         ctx.holder = holder
         ctx.params = (Wm, Wp, bm, bp)
-        if any(ctx.needs_input_grad):
+        if grad_mode and any(ctx.needs_input_grad):
             # the backward runs on single bf16 operands like every other Linear backward: bf16 copies of the inputs (shared with the
             # other consumers of `memory` / `pos`) and the transposed bf16 weight stack for the input gradient
             m16, _ = K.act16(m2, memory)
