@@ -9,18 +9,6 @@
 // Timing-experiment switches (SPE_DBG_*, SPE_ABL_*, plain-store variants) exist only in -DSPE_ABLATE builds (tools/ab.py); the
 // product library (spe_amd/build.py) never defines SPE_ABLATE, so none of them can change what a parity or benchmark run executes.
 #ifndef SPE_ABLATE
-#undef SPE_DBG_NOEXP
-#undef SPE_DBG_NOMIX
-#undef SPE_DBG_TAILNOP
-#undef SPE_DBG_NOKEEP
-#undef SPE_DBG_NOSTAGE
-#undef SPE_DBG_NOLOAD
-#undef SPE_DBG_NOGW
-#undef SPE_DBG_NOMIX4
-#undef SPE_DBG_NOMM
-#undef SPE_DBG_NOGWM
-#undef SPE_DBG_NOST3
-#undef SPE_DBG_LN_NOATOMIC
 #undef SPE_ABL_NOSTORE
 #undef SPE_ABL_NOLOOP
 #undef SPE_PLAIN_STORES
@@ -30,6 +18,8 @@
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
@@ -41,6 +31,25 @@ __device__ __forceinline__ unsigned short spe_f2bf(float f) {
 }
 __device__ __forceinline__ float spe_bf2f(unsigned short h) {
     return __uint_as_float(((uint32_t)h) << 16);
+}
+// four fp32 -> bf16 by the compiler's own conversion (round-to-nearest-even, NaN kept; not the integer path above), as the 8 bytes a lane stores
+__device__ __forceinline__ uint2 spe_pack_bf16x4(float4 v) {
+    bf16x4_t h;
+    h[0] = (__bf16)v.x; h[1] = (__bf16)v.y; h[2] = (__bf16)v.z; h[3] = (__bf16)v.w;
+    return __builtin_bit_cast(uint2, h);
+}
+
+// float4 arithmetic of the row kernels, component by component.  Each helper is the expression its callers used to spell out, so
+// after inlining every multiply-add contracts (or not) exactly as before and every sum keeps its order.
+__device__ __forceinline__ float spe_hsum(float4 v) { return v.x + v.y + v.z + v.w; }
+__device__ __forceinline__ float spe_sqdev(float4 v, float mu) {          // sum of squared deviations from mu
+    const float a = v.x - mu, b = v.y - mu, d = v.z - mu, e = v.w - mu;
+    return a * a + b * b + d * d + e * e;
+}
+__device__ __forceinline__ float4 spe_add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float4 spe_mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+__device__ __forceinline__ void spe_fma4(float4& acc, float4 a, float4 b) {          // acc += a * b
+    acc.x += a.x * b.x; acc.y += a.y * b.y; acc.z += a.z * b.z; acc.w += a.w * b.w;
 }
 
 // erf(x) in fp32, branch-free (both polynomial branches are evaluated and selected: ~20 instructions against the ~100
@@ -168,16 +177,14 @@ __device__ __forceinline__ void spe_drop_scale4(uint64_t seed, uint64_t offset, 
 // second 16-bit copy of 4 values next to their bf16 copy h: the low part of a split bf16 operand, bf16(v - bf16(v)), or - lo_f16 - the
 // IEEE fp16 copy (saturating, NaN kept) that single-term fp16 forward products read (round 5: the backbone MLP of precision mode bf16s)
 __device__ __forceinline__ uint2 spe_second16(const float (&v)[4], uint2 hi_bits, bool lo_f16) {
-    typedef __bf16 spe_bf16x4s_t __attribute__((ext_vector_type(4)));
-    typedef _Float16 spe_h4s_t __attribute__((ext_vector_type(4)));
     if (lo_f16) {
-        spe_h4s_t h;
+        f16x4_t h;
 #pragma unroll
         for (int k = 0; k < 4; ++k) h[k] = (_Float16)((v[k] != v[k]) ? v[k] : __builtin_amdgcn_fmed3f(v[k], -65504.f, 65504.f));
         return __builtin_bit_cast(uint2, h);
     }
-    const spe_bf16x4s_t hb = __builtin_bit_cast(spe_bf16x4s_t, hi_bits);
-    spe_bf16x4s_t l;
+    const bf16x4_t hb = __builtin_bit_cast(bf16x4_t, hi_bits);
+    bf16x4_t l;
 #pragma unroll
     for (int k = 0; k < 4; ++k) l[k] = (__bf16)(v[k] - (float)hb[k]);
     return __builtin_bit_cast(uint2, l);

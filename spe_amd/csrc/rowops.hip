@@ -2,7 +2,6 @@
 // column sums (bias / gamma gradients), LayerScale-residual, GELU/ReLU backward, dropout.
 // All tensors fp32, row-major, contiguous unless a stride is passed.  HBM-bound kernels:
 // every lane moves 16 B per access where the row length allows it.
-#include <cstdlib>
 #include "common.h"
 #include "det_reduce.h"
 
@@ -12,11 +11,37 @@
 // ------------------------------------------------------------------------------------------
 #define LN_MAXV 4  // float4 per lane -> C <= 1024
 
-__global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                     const float* __restrict__ beta, float* __restrict__ y,
+// The forward of one row, as both forward kernels run it on the float4s v a lane holds: s += spe_hsum(v) summed over the row -> mu,
+// q += spe_sqdev(v, mu) summed over the row -> rs = rsqrt(q / C + eps), then this for the lane's column quad c of the row that starts at element ro = row * C.
+// Only the lane mapping and the reduction tree belong to the kernel.  The address stays split into the row offset and the column quad, as
+// the stores index it: handed the element index ro + 4 c instead, ln_fwd_hw_kernel<2..4> lose an occupancy step.
+__device__ __forceinline__ void ln_store4(float4 v, float mu, float rs, float4 g, float4 b, long ro, int c, float* __restrict__ y,
+                                          unsigned short* __restrict__ y16, unsigned short* __restrict__ y16lo, bool lo_f16) {
+    float4 o;
+    o.x = (v.x - mu) * rs * g.x + b.x; o.y = (v.y - mu) * rs * g.y + b.y;
+    o.z = (v.z - mu) * rs * g.z + b.z; o.w = (v.w - mu) * rs * g.w + b.w;
+    reinterpret_cast<float4*>(y + ro)[c] = o;
+    if (y16) {      // the bf16 operand of the Linear that consumes y (same rounding as spe_cvt_bf16), from the same pass
+        const uint2 h = spe_pack_bf16x4(o);
+        *reinterpret_cast<uint2*>(y16 + ro + 4 * c) = h;
+        if (y16lo) {    // low part of the split operand (precision mode bf16s): bf16(y - bf16(y)) - or the fp16 copy (lo_f16)
+            const float ov[4] = {o.x, o.y, o.z, o.w};
+            *reinterpret_cast<uint2*>(y16lo + ro + 4 * c) = spe_second16(ov, h, lo_f16);
+        }
+    }
+}
+
+// RES: the post-norm residual site of the DETR encoder / decoder layers, `norm(x + dropout(z))` (reference models/transformer.py:
+// 279-287, 384-386, 420-421, 426-427), as ONE pass: s = x + z * keepscale(row*C + c) is written to `sum` (LayerNorm's input, kept for
+// the backward) and normalised by the very code that normalises x when !RES; no 16-bit copies there.  The dropout stream is that of
+// dropout_kernel (element index row*C + c), so the fused and the unfused composition draw the same mask.
+template <bool RES>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ z,
+                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                     float* __restrict__ sum, float* __restrict__ y,
                                                      float* __restrict__ mean, float* __restrict__ rstd,
                                                      long R, int C, float eps, unsigned short* __restrict__ y16,
-                                                     unsigned short* __restrict__ y16lo, bool lo_f16) {
+                                                     unsigned short* __restrict__ y16lo, bool lo_f16, float p, uint64_t seed, uint64_t offset) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= R) return;
@@ -27,48 +52,79 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 #pragma unroll
     for (int i = 0; i < LN_MAXV; ++i) {
         const int c = lane + 64 * i;
-        if (c < C4) { v[i] = xr[c]; s += v[i].x + v[i].y + v[i].z + v[i].w; }
+        if (c < C4) {
+            v[i] = xr[c];
+            if constexpr (RES) {
+                float4 b = reinterpret_cast<const float4*>(z + row * C)[c];
+                if (p > 0.f) {
+                    float ks[4];
+                    spe_drop_scale4(seed, offset, (uint64_t)(row * C + 4 * c), p, ks);
+                    b.x *= ks[0]; b.y *= ks[1]; b.z *= ks[2]; b.w *= ks[3];
+                }
+                v[i] = spe_add4(v[i], b);
+                reinterpret_cast<float4*>(sum + row * C)[c] = v[i];
+            }
+            s += spe_hsum(v[i]);
+        }
     }
     const float mu = spe_wave_sum(s) / (float)C;
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C4) {
-            const float a = v[i].x - mu, b = v[i].y - mu, d = v[i].z - mu, e = v[i].w - mu;
-            q += a * a + b * b + d * d + e * e;
-        }
-    }
+    for (int i = 0; i < LN_MAXV; ++i)
+        if (lane + 64 * i < C4) q += spe_sqdev(v[i], mu);
     const float rs = rsqrtf(spe_wave_sum(q) / (float)C + eps);
     if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
-    float4* yr = reinterpret_cast<float4*>(y + row * C);
     const float4* g4 = reinterpret_cast<const float4*>(gamma);
     const float4* b4 = reinterpret_cast<const float4*>(beta);
 #pragma unroll
     for (int i = 0; i < LN_MAXV; ++i) {
         const int c = lane + 64 * i;
-        if (c < C4) {
-            const float4 g = g4[c], b = b4[c];
-            float4 o;
-            o.x = (v[i].x - mu) * rs * g.x + b.x; o.y = (v[i].y - mu) * rs * g.y + b.y;
-            o.z = (v[i].z - mu) * rs * g.z + b.z; o.w = (v[i].w - mu) * rs * g.w + b.w;
-            yr[c] = o;
-            if (y16) {      // the bf16 operand of the Linear that consumes y (same rounding as spe_cvt_bf16), from the same pass
-                typedef __bf16 bf16x4l_t __attribute__((ext_vector_type(4)));
-                bf16x4l_t h;
-                h[0] = (__bf16)o.x; h[1] = (__bf16)o.y; h[2] = (__bf16)o.z; h[3] = (__bf16)o.w;
-                *reinterpret_cast<uint2*>(y16 + row * C + 4 * c) = __builtin_bit_cast(uint2, h);
-                if (y16lo) {    // low part of the split operand (precision mode bf16s): bf16(y - bf16(y)) - or the fp16 copy (lo_f16)
-                    const float ov[4] = {o.x, o.y, o.z, o.w};
-                    *reinterpret_cast<uint2*>(y16lo + row * C + 4 * c) = spe_second16(ov, __builtin_bit_cast(uint2, h), lo_f16);
-                }
-            }
-        }
+        if (c < C4) ln_store4(v[i], mu, rs, g4[c], b4[c], row * C, c, y, RES ? nullptr : y16, y16lo, lo_f16);
     }
 }
 
+// Fixed-order column sums of the backward kernels below.  Every wave of the workgroup holds K sets of per-lane float4 accumulators
+// (acc[k][i]: columns 4 (lane + 64 i) .. + 3 of set k, over the rows that wave took).  They go to LDS as red[K][NW][C + 4]; after the
+// barrier det_reduce (det_reduce.h) adds the NW waves in index order, then the workgroups in a fixed order: value k * C + c of
+// L = K * C per workgroup, and store(k, c, total) runs once per column of every set.
+template <int K, int NW, int MAXV, class S>
+__device__ __forceinline__ void wave_cols_reduce(float* red, const float4* const* acc, int C, const DetWs& ws, S store) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int C4 = C >> 2, ldr = C + 4;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int c = lane + 64 * i;
+        if (c < C4) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {          // written per component, as ln_bwd_kernel always did (ds_write2_b32 pairs)
+                float* r = red + (long)(k * NW + w) * ldr + 4 * c;
+                r[0] = acc[k][i].x; r[1] = acc[k][i].y; r[2] = acc[k][i].z; r[3] = acc[k][i].w;
+            }
+        }
+    }
+    __syncthreads();
+    auto set_of = [&](int c) {          // c / C for c < K * C, without the division
+        int k = 0;
+#pragma unroll
+        for (int j = 1; j < K; ++j) k += c >= j * C;
+        return k;
+    };
+    det_reduce(ws, 0, blockIdx.x, gridDim.x, K * C, threadIdx.x, NW * 64,
+               [&](int c) {
+                   const int k = set_of(c), cc = c - k * C;
+                   float t = 0.f;
+#pragma unroll
+                   for (int wv = 0; wv < NW; ++wv) t += red[(long)(k * NW + wv) * ldr + cc];
+                   return t;
+               },
+               [&](int c, float t) {
+                   const int k = set_of(c);
+                   store(k, c - k * C, t);
+               });
+}
+
 // dx per row; dgamma/dbeta accumulated per wave in registers over a grid-stride row loop, combined through LDS, then across
-// the workgroups in a fixed order (det_reduce.h) and added to the running gradient.
+// the workgroups in a fixed order (wave_cols_reduce) and added to the running gradient.
 // LS (round 5): the LayerScale backward of the node that CONSUMES dx - dx is the `dout` of out = res + ls_gamma * ls_y (the branch Linear before this
 // norm's input, reference models/cait.py:404-405) - rides on the same pass: ls_dy16 = bf16(ls_gamma * dx) (the operand of that Linear's backward GEMMs),
 // ls_db += sum_r ls_gamma * dx (its bias gradient), ls_dg += sum_r dx * ls_y (the LayerScale gradient) - what spe_layerscale_residual_bwd16 would compute
@@ -83,8 +139,6 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const float* __restrict
                                                      const float* __restrict__ ls_y, const float* __restrict__ ls_gamma,
                                                      unsigned short* __restrict__ ls_dy16, float* __restrict__ ls_db, float* __restrict__ ls_dg) {
     extern __shared__ float red_raw[];                 // [2 (LS: 4)][NW][C + 4]
-    const int ldr = C + 4;
-    auto red = [&](int k, int wv, int c) -> float& { return red_raw[((long)k * NW + wv) * ldr + c]; };
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int C4 = C >> 2;
     const float4* g4 = reinterpret_cast<const float4*>(gamma);
@@ -107,15 +161,15 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const float* __restrict
         for (int i = 0; i < MAXV; ++i) {
             const int c = lane + 64 * i;
             if (c < C4) {
-                const float4 xv = xr[c], g = g4[c];
+                const float4 xv = xr[c], g = g4[c];          // all three loads ahead of the dr2 branch
                 float4 dv = dr[c];
-                if (dr2) { const float4 d2 = dr2[c]; dv.x += d2.x; dv.y += d2.y; dv.z += d2.z; dv.w += d2.w; }
+                if (dr2) dv = spe_add4(dv, dr2[c]);
                 xh[i].x = (xv.x - mu) * rs; xh[i].y = (xv.y - mu) * rs; xh[i].z = (xv.z - mu) * rs; xh[i].w = (xv.w - mu) * rs;
-                dg[i].x = dv.x * g.x; dg[i].y = dv.y * g.y; dg[i].z = dv.z * g.z; dg[i].w = dv.w * g.w;
-                s1 += dg[i].x + dg[i].y + dg[i].z + dg[i].w;
+                dg[i] = spe_mul4(dv, g);
+                s1 += spe_hsum(dg[i]);
                 s2 += dg[i].x * xh[i].x + dg[i].y * xh[i].y + dg[i].z * xh[i].z + dg[i].w * xh[i].w;
-                ag[i].x += dv.x * xh[i].x; ag[i].y += dv.y * xh[i].y; ag[i].z += dv.z * xh[i].z; ag[i].w += dv.w * xh[i].w;
-                ab[i].x += dv.x; ab[i].y += dv.y; ab[i].z += dv.z; ab[i].w += dv.w;
+                spe_fma4(ag[i], dv, xh[i]);
+                ab[i] = spe_add4(ab[i], dv);
             }
         }
         s1 = spe_wave_sum(s1) / (float)C;
@@ -129,19 +183,15 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const float* __restrict
                 float4 o;
                 o.x = rs * (dg[i].x - s1 - xh[i].x * s2); o.y = rs * (dg[i].y - s1 - xh[i].y * s2);
                 o.z = rs * (dg[i].z - s1 - xh[i].z * s2); o.w = rs * (dg[i].w - s1 - xh[i].w * s2);
-                if (ar) { const float4 a4 = ar[c]; o.x += a4.x; o.y += a4.y; o.z += a4.z; o.w += a4.w; }   // + gradient of the skip path
+                if (ar) o = spe_add4(o, ar[c]);   // + gradient of the skip path
                 dxr[c] = o;
                 if constexpr (LS) {
-                    const float4 yv = reinterpret_cast<const float4*>(ls_y + row * C)[c], gg = reinterpret_cast<const float4*>(ls_gamma)[c];
-                    lg[i].x += o.x * yv.x; lg[i].y += o.y * yv.y; lg[i].z += o.z * yv.z; lg[i].w += o.w * yv.w;
-                    const float4 q = make_float4(o.x * gg.x, o.y * gg.y, o.z * gg.z, o.w * gg.w);
-                    lb[i].x += q.x; lb[i].y += q.y; lb[i].z += q.z; lb[i].w += q.w;
-                    typedef __bf16 bf16x4n_t __attribute__((ext_vector_type(4)));
-                    bf16x4n_t h;
-                    h[0] = (__bf16)q.x; h[1] = (__bf16)q.y; h[2] = (__bf16)q.z; h[3] = (__bf16)q.w;
-                    *reinterpret_cast<uint2*>(ls_dy16 + row * C + 4 * c) = __builtin_bit_cast(uint2, h);
+                    spe_fma4(lg[i], o, reinterpret_cast<const float4*>(ls_y + row * C)[c]);
+                    const float4 q = spe_mul4(o, reinterpret_cast<const float4*>(ls_gamma)[c]);
+                    lb[i] = spe_add4(lb[i], q);
+                    *reinterpret_cast<uint2*>(ls_dy16 + row * C + 4 * c) = spe_pack_bf16x4(q);
                 }
-                if (dz) {          // gradient of the dropped branch of norm(x + dropout(z)): same mask as ln_res_fwd_kernel
+                if (dz) {          // gradient of the dropped branch of norm(x + dropout(z)): same mask as ln_fwd_kernel<true>
                     float ks[4];
                     spe_drop_scale4(seed, offset, (uint64_t)(row * C + 4 * c), p, ks);
                     reinterpret_cast<float4*>(dz + row * C)[c] = make_float4(o.x * ks[0], o.y * ks[1], o.z * ks[2], o.w * ks[3]);
@@ -149,101 +199,19 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const float* __restrict
             }
         }
     }
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C4) {
-            red(0, w, 4 * c + 0) = ag[i].x; red(0, w, 4 * c + 1) = ag[i].y; red(0, w, 4 * c + 2) = ag[i].z; red(0, w, 4 * c + 3) = ag[i].w;
-            red(1, w, 4 * c + 0) = ab[i].x; red(1, w, 4 * c + 1) = ab[i].y; red(1, w, 4 * c + 2) = ab[i].z; red(1, w, 4 * c + 3) = ab[i].w;
-            if constexpr (LS) {
-                red(2, w, 4 * c + 0) = lg[i].x; red(2, w, 4 * c + 1) = lg[i].y; red(2, w, 4 * c + 2) = lg[i].z; red(2, w, 4 * c + 3) = lg[i].w;
-                red(3, w, 4 * c + 0) = lb[i].x; red(3, w, 4 * c + 1) = lb[i].y; red(3, w, 4 * c + 2) = lb[i].z; red(3, w, 4 * c + 3) = lb[i].w;
-            }
-        }
-    }
-    __syncthreads();
-    // the 16 waves' column sums in wave order, then across workgroups in a fixed order (det_reduce.h): dgamma / dbeta (/ ls_dg / ls_db) += total
-    det_reduce(ws, 0, blockIdx.x, gridDim.x, (LS ? 4 : 2) * C, threadIdx.x, NW * 64,
-               [&](int c) {
-                   const int k = c / C, cc = c - k * C;
-                   float t = 0.f;
-#pragma unroll
-                   for (int wv = 0; wv < NW; ++wv) t += red(k, wv, cc);
-                   return t;
-               },
-               [&](int c, float t) {
-                   const int k = c / C, cc = c - k * C;
-                   float* d = (k == 0) ? dgamma : ((k == 1) ? dbeta : ((k == 2) ? ls_dg : ls_db));
-                   d[cc] += t;
-               });
-}
-
-// Post-norm residual site of the DETR encoder / decoder layers, `norm(x + dropout(z))` (reference models/transformer.py:
-// 279-287, 384-386, 420-421, 426-427), as ONE pass: s = x + z * keepscale(row*C + c) is written (LayerNorm's input, kept for
-// the backward), then normalised exactly like ln_fwd_kernel.  The dropout stream is that of dropout_kernel (element index
-// row*C + c), so the fused and the unfused composition draw the same mask.
-__global__ __launch_bounds__(256) void ln_res_fwd_kernel(const float* __restrict__ x, const float* __restrict__ z,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         float* __restrict__ sum, float* __restrict__ y, float* __restrict__ mean,
-                                                         float* __restrict__ rstd, long R, int C, float eps, float p,
-                                                         uint64_t seed, uint64_t offset) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= R) return;
-    const int C4 = C >> 2;
-    const float4* xr = reinterpret_cast<const float4*>(x + row * C);
-    const float4* zr = reinterpret_cast<const float4*>(z + row * C);
-    float4* sr = reinterpret_cast<float4*>(sum + row * C);
-    float4 v[LN_MAXV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C4) {
-            const float4 a = xr[c];
-            float4 b = zr[c];
-            if (p > 0.f) {
-                float ks[4];
-                spe_drop_scale4(seed, offset, (uint64_t)(row * C + 4 * c), p, ks);
-                b.x *= ks[0]; b.y *= ks[1]; b.z *= ks[2]; b.w *= ks[3];
-            }
-            v[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-            sr[c] = v[i];
-            s += v[i].x + v[i].y + v[i].z + v[i].w;
-        }
-    }
-    const float mu = spe_wave_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C4) {
-            const float a = v[i].x - mu, b = v[i].y - mu, d = v[i].z - mu, e = v[i].w - mu;
-            q += a * a + b * b + d * d + e * e;
-        }
-    }
-    const float rs = rsqrtf(spe_wave_sum(q) / (float)C + eps);
-    if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
-    float4* yr = reinterpret_cast<float4*>(y + row * C);
-    const float4* g4 = reinterpret_cast<const float4*>(gamma);
-    const float4* b4 = reinterpret_cast<const float4*>(beta);
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C4) {
-            const float4 g = g4[c], b = b4[c];
-            float4 o;
-            o.x = (v[i].x - mu) * rs * g.x + b.x; o.y = (v[i].y - mu) * rs * g.y + b.y;
-            o.z = (v[i].z - mu) * rs * g.z + b.z; o.w = (v[i].w - mu) * rs * g.w + b.w;
-            yr[c] = o;
-        }
-    }
+    // dgamma / dbeta (/ ls_dg / ls_db) += total.  The pointer table must fold away (full unrolling) so that the accumulators stay in
+    // registers; !LS never reads lg / lb through it (K = 2).  Re-check that scratch is 0 after any edit here.
+    const float4* const acc[4] = {ag, ab, lg, lb};
+    wave_cols_reduce<LS ? 4 : 2, NW, MAXV>(red_raw, acc, C, ws, [&](int k, int c, float t) {
+        float* d = (k == 0) ? dgamma : ((k == 1) ? dbeta : ((k == 2) ? ls_dg : ls_db));
+        d[c] += t;
+    });
 }
 
 // Half-wave-per-row variant for C = 128 * NV (NV <= 4: 128, 256, 384, 512 - every model width here): a wave normalises TWO rows,
 // 32 lanes each, so no lane idles (C = 384 is 96 float4: 64 + 32 in the wave-per-row mapping) and a lane keeps NV 16-B loads in
-// flight instead of 1.5 on average; the reductions are 5 DPP steps inside the half.  Same arithmetic order per row element
-// as ln_fwd_kernel up to the reduction tree.
+// flight instead of 1.5 on average; the reductions are 5 DPP steps inside the half.  The row steps are those of ln_fwd_kernel
+// (spe_hsum, spe_sqdev, ln_store4): the same arithmetic per row element up to the reduction tree.
 template <int NV>
 __global__ __launch_bounds__(256) void ln_fwd_hw_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float* __restrict__ y,
@@ -279,56 +247,43 @@ __global__ __launch_bounds__(256) void ln_fwd_hw_kernel(const float* __restrict_
         }
         float s = 0.f;
 #pragma unroll
-        for (int i = 0; i < NV; ++i) s += v[i].x + v[i].y + v[i].z + v[i].w;
+        for (int i = 0; i < NV; ++i) s += spe_hsum(v[i]);
 #pragma unroll
         for (int o = 16; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
         const float mu = s / (float)C;
         float q = 0.f;
 #pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const float a = v[i].x - mu, b = v[i].y - mu, d = v[i].z - mu, e = v[i].w - mu;
-            q += a * a + b * b + d * d + e * e;
-        }
+        for (int i = 0; i < NV; ++i) q += spe_sqdev(v[i], mu);
 #pragma unroll
         for (int o = 16; o >= 1; o >>= 1) q += __shfl_xor(q, o, 64);
         const float rs = rsqrtf(q / (float)C + eps);
         if (rv) {
             if (hl == 0) { mean[row] = mu; rstd[row] = rs; }
-            float4* yr = reinterpret_cast<float4*>(y + row * C);
 #pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int c = hl + 32 * i;
-                float4 o;
-                o.x = (v[i].x - mu) * rs * gq[i].x + bq[i].x; o.y = (v[i].y - mu) * rs * gq[i].y + bq[i].y;
-                o.z = (v[i].z - mu) * rs * gq[i].z + bq[i].z; o.w = (v[i].w - mu) * rs * gq[i].w + bq[i].w;
-                yr[c] = o;
-                if (y16) {
-                    typedef __bf16 bf16x4h_t __attribute__((ext_vector_type(4)));
-                    bf16x4h_t h;
-                    h[0] = (__bf16)o.x; h[1] = (__bf16)o.y; h[2] = (__bf16)o.z; h[3] = (__bf16)o.w;
-                    *reinterpret_cast<uint2*>(y16 + row * C + 4 * c) = __builtin_bit_cast(uint2, h);
-                    if (y16lo) {
-                        const float ov[4] = {o.x, o.y, o.z, o.w};
-                        *reinterpret_cast<uint2*>(y16lo + row * C + 4 * c) = spe_second16(ov, __builtin_bit_cast(uint2, h), lo_f16);
-                    }
-                }
-            }
+            for (int i = 0; i < NV; ++i) ln_store4(v[i], mu, rs, gq[i], bq[i], row * C, hl + 32 * i, y, y16, y16lo, lo_f16);
         }
 #pragma unroll
         for (int i = 0; i < NV; ++i) v[i] = nv[i];
     }
 }
 
+// the arguments the wave-per-row kernel takes in both forms, once
+template <bool RES>
+static int ln_fwd_rows_launch(const float* x, const float* z, const float* gamma, const float* beta, float* sum, float* y, float* mean,
+                              float* rstd, long R, int C, float eps, void* y16, void* y16lo, bool lo_f16, float p, uint64_t seed,
+                              uint64_t offset, hipStream_t st) {
+    hipLaunchKernelGGL(ln_fwd_kernel<RES>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, x, z, gamma, beta, sum, y, mean, rstd, R, C, eps,
+                       reinterpret_cast<unsigned short*>(y16), reinterpret_cast<unsigned short*>(y16lo), lo_f16, p, seed, offset);
+    SPE_CHECK_LAUNCH();
+    return 0;
+}
 // C-ABI: see include/spe_hip.h (spe_layernorm_res_fwd).
 extern "C" int spe_layernorm_res_fwd(const float* x, const float* z, const float* gamma, const float* beta, float* sum, float* y,
                                      float* mean, float* rstd, long R, int C, float eps, float p, uint64_t seed, uint64_t offset,
                                      hipStream_t st) {
     if (R <= 0) return 0;
     if ((C & 3) || C > 256 * LN_MAXV) return -2;
-    hipLaunchKernelGGL(ln_res_fwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, x, z, gamma, beta, sum, y, mean, rstd, R, C,
-                       eps, p, seed, offset);
-    SPE_CHECK_LAUNCH();
-    return 0;
+    return ln_fwd_rows_launch<true>(x, z, gamma, beta, sum, y, mean, rstd, R, C, eps, nullptr, nullptr, false, p, seed, offset, st);
 }
 
 static int ln_fwd_launch(const float* x, const float* gamma, const float* beta, float* y, float* mean,
@@ -336,23 +291,14 @@ static int ln_fwd_launch(const float* x, const float* gamma, const float* beta, 
     if (R <= 0) return 0;
     if ((C & 3) || C > 256 * LN_MAXV || (y16lo && !y16)) return -2;
     if ((C % 128) == 0 && C <= 512) {          // half-wave-per-row kernel
+        static constexpr decltype(&ln_fwd_hw_kernel<1>) hw[4] = {ln_fwd_hw_kernel<1>, ln_fwd_hw_kernel<2>, ln_fwd_hw_kernel<3>, ln_fwd_hw_kernel<4>};
         long nwg_ = (R + 7) / 8; if (nwg_ > 512) nwg_ = 512;
-        const dim3 grid((unsigned)nwg_);
-        unsigned short* h16 = reinterpret_cast<unsigned short*>(y16);
-        unsigned short* l16 = reinterpret_cast<unsigned short*>(y16lo);
-        switch (C / 128) {
-            case 1: hipLaunchKernelGGL(ln_fwd_hw_kernel<1>, grid, dim3(256), 0, st, x, gamma, beta, y, mean, rstd, R, eps, h16, l16, lo_f16); break;
-            case 2: hipLaunchKernelGGL(ln_fwd_hw_kernel<2>, grid, dim3(256), 0, st, x, gamma, beta, y, mean, rstd, R, eps, h16, l16, lo_f16); break;
-            case 3: hipLaunchKernelGGL(ln_fwd_hw_kernel<3>, grid, dim3(256), 0, st, x, gamma, beta, y, mean, rstd, R, eps, h16, l16, lo_f16); break;
-            default: hipLaunchKernelGGL(ln_fwd_hw_kernel<4>, grid, dim3(256), 0, st, x, gamma, beta, y, mean, rstd, R, eps, h16, l16, lo_f16); break;
-        }
+        hipLaunchKernelGGL(hw[C / 128 - 1], dim3((unsigned)nwg_), dim3(256), 0, st, x, gamma, beta, y, mean, rstd, R, eps,
+                           reinterpret_cast<unsigned short*>(y16), reinterpret_cast<unsigned short*>(y16lo), lo_f16);
         SPE_CHECK_LAUNCH();
         return 0;
     }
-    hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, x, gamma, beta, y, mean, rstd, R, C, eps,
-                       reinterpret_cast<unsigned short*>(y16), reinterpret_cast<unsigned short*>(y16lo), lo_f16);
-    SPE_CHECK_LAUNCH();
-    return 0;
+    return ln_fwd_rows_launch<false>(x, nullptr, gamma, beta, nullptr, y, mean, rstd, R, C, eps, y16, y16lo, lo_f16, 0.f, 0, 0, st);
 }
 // C-ABI: see include/spe_hip.h
 extern "C" int spe_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean,
@@ -375,29 +321,26 @@ static int ln_bwd_launch(const float* dy, const float* x, const float* gamma, co
                ((reinterpret_cast<uintptr_t>(ls_y) | reinterpret_cast<uintptr_t>(ls_gamma) | reinterpret_cast<uintptr_t>(ls_dy16)) & 15))) return -2;
     // 16 waves per workgroup, at most 256 workgroups: every workgroup ends with a 2*C-value (LS: 4*C) partial for the cross-workgroup sum
     constexpr int NW = 16;
+    // the instantiation: LS (C <= 512), 2 float4 per lane up to C = 512, LN_MAXV above
+    static constexpr decltype(&ln_bwd_kernel<NW, false, 2>) kernels[3] = {ln_bwd_kernel<NW, true, 2>, ln_bwd_kernel<NW, false, 2>,
+                                                                          ln_bwd_kernel<NW, false, LN_MAXV>};
     static bool attr[3] = {false, false, false};
-    const int variant = ls ? 1 : (C <= 512 ? 2 : 0);
+    const int variant = ls ? 0 : (C <= 512 ? 1 : 2);
+    const int nk = ls ? 4 : 2;
     if (!attr[variant]) {
-        const void* fn = ls ? reinterpret_cast<const void*>(&ln_bwd_kernel<NW, true, 2>)
-                            : (C <= 512 ? reinterpret_cast<const void*>(&ln_bwd_kernel<NW, false, 2>) : reinterpret_cast<const void*>(&ln_bwd_kernel<NW, false, LN_MAXV>));
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           ls ? 4 * NW * (512 + 4) * (int)sizeof(float) : 2 * NW * (256 * LN_MAXV + 4) * (int)sizeof(float));
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[variant]), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           nk * NW * ((ls ? 512 : 256 * LN_MAXV) + 4) * (int)sizeof(float));
         if (e != hipSuccess) return (int)e;
         attr[variant] = true;
     }
     long nb = (R + NW - 1) / NW; if (nb > 256) nb = 256;
     DetWs ws = spe_detws();
-    const int nk = ls ? 4 : 2;
     // deferred (destinations inside the registered bucket ranges): the workgroups leave their partials behind, the totals land at the next flush
     const DetDeferSeg sg[4] = {{dgamma, C}, {dbeta, C}, {ls_dg, C}, {ls_db, C}};
     float* region = det_defer_try(1, nb, nk * C, nk, sg, st);
     if (region) ws.defer = region; else DET_CHECK(ws, 1, nb, nk * C);
-    if (ls) hipLaunchKernelGGL((ln_bwd_kernel<NW, true, 2>), dim3((unsigned)nb), dim3(NW * 64), 4 * NW * (C + 4) * (int)sizeof(float), st, dy, x, gamma, mean,
-                               rstd, dx, dgamma, dbeta, R, C, add, dz, p, seed, offset, ws, dy2, ls_y, ls_gamma, reinterpret_cast<unsigned short*>(ls_dy16), ls_db, ls_dg);
-    else if (C <= 512) hipLaunchKernelGGL((ln_bwd_kernel<NW, false, 2>), dim3((unsigned)nb), dim3(NW * 64), 2 * NW * (C + 4) * (int)sizeof(float), st, dy, x, gamma, mean,
-                                          rstd, dx, dgamma, dbeta, R, C, add, dz, p, seed, offset, ws, dy2, nullptr, nullptr, nullptr, nullptr, nullptr);
-    else hipLaunchKernelGGL((ln_bwd_kernel<NW, false, LN_MAXV>), dim3((unsigned)nb), dim3(NW * 64), 2 * NW * (C + 4) * (int)sizeof(float), st, dy, x, gamma, mean,
-                            rstd, dx, dgamma, dbeta, R, C, add, dz, p, seed, offset, ws, dy2, nullptr, nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(kernels[variant], dim3((unsigned)nb), dim3(NW * 64), nk * NW * (C + 4) * (int)sizeof(float), st, dy, x, gamma, mean,
+                       rstd, dx, dgamma, dbeta, R, C, add, dz, p, seed, offset, ws, dy2, ls_y, ls_gamma, reinterpret_cast<unsigned short*>(ls_dy16), ls_db, ls_dg);
     if (region) det_defer_commit(region, 1, nb, nk * C, nk, sg, 1);
     SPE_CHECK_LAUNCH();
     return 0;
@@ -517,8 +460,7 @@ __global__ __launch_bounds__(256) void colsum_wide_kernel(const float* __restric
     float4 acc = accumulate ? *reinterpret_cast<const float4*>(out + c) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 4
     for (int r = 0; r < R; ++r) {
-        const float4 v = *reinterpret_cast<const float4*>(in + r * ld + c);
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+        acc = spe_add4(acc, *reinterpret_cast<const float4*>(in + r * ld + c));
     }
     *reinterpret_cast<float4*>(out + c) = acc;
 }
@@ -529,10 +471,8 @@ __global__ __launch_bounds__(256) void colsum_tall4_kernel(const float* __restri
     const int c = (blockIdx.x * 16 + cq) * 4;
     float4 acc = {0.f, 0.f, 0.f, 0.f};
     if (c < C)
-        for (long r = (long)blockIdx.y * 16 + rl; r < R; r += (long)gridDim.y * 16) {
-            const float4 v = *reinterpret_cast<const float4*>(in + r * ld + c);
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
+        for (long r = (long)blockIdx.y * 16 + rl; r < R; r += (long)gridDim.y * 16)
+            acc = spe_add4(acc, *reinterpret_cast<const float4*>(in + r * ld + c));
     red[rl][cq] = acc;
     __syncthreads();
     // 16 row lanes in order, then the row segments (blockIdx.y) in order: det_reduce.h
@@ -624,7 +564,7 @@ __global__ __launch_bounds__(256) void lsres_bwd_kernel(const float* __restrict_
                [&](int k, float s) { const int cc = blockIdx.x * 64 + k; if (cc < C) dgamma[cc] += s; });
 }
 // The same, one wave per row with 16-B accesses and per-lane column accumulators (C % 4 == 0, C <= 256 * LN_MAXV):
-// NW = 16 waves per workgroup so that few workgroups (few atomics per column) still fill the SIMDs.
+// NW = 16 waves per workgroup so that few workgroups (few partial rows in the fixed-order sum across them) still fill the SIMDs.
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void lsres_bwd_rows_kernel(const float* __restrict__ dout, const float* __restrict__ y,
                                                                  const float* __restrict__ gamma, const float* __restrict__ sample_scale,
@@ -632,7 +572,7 @@ __global__ __launch_bounds__(NW * 64) void lsres_bwd_rows_kernel(const float* __
                                                                  long rows_per_sample, DetWs ws) {
     extern __shared__ float red_raw[];                 // [NW][C + 4]
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int C4 = C >> 2, ldr = C + 4;
+    const int C4 = C >> 2;
     const float4* g4 = reinterpret_cast<const float4*>(gamma);
     float4 acc[LN_MAXV], g[LN_MAXV];
 #pragma unroll
@@ -653,25 +593,13 @@ __global__ __launch_bounds__(NW * 64) void lsres_bwd_rows_kernel(const float* __
                 float4 d = dr[c];
                 const float4 yv = yr[c];
                 d.x *= sc; d.y *= sc; d.z *= sc; d.w *= sc;
-                acc[i].x += d.x * yv.x; acc[i].y += d.y * yv.y; acc[i].z += d.z * yv.z; acc[i].w += d.w * yv.w;
-                o[c] = make_float4(d.x * g[i].x, d.y * g[i].y, d.z * g[i].z, d.w * g[i].w);
+                spe_fma4(acc[i], d, yv);
+                o[c] = spe_mul4(d, g[i]);
             }
         }
     }
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C4) *reinterpret_cast<float4*>(red_raw + (long)w * ldr + 4 * c) = acc[i];
-    }
-    __syncthreads();
-    det_reduce(ws, 0, blockIdx.x, gridDim.x, C, threadIdx.x, NW * 64,
-               [&](int c) {
-                   float t = 0.f;
-#pragma unroll
-                   for (int wv = 0; wv < NW; ++wv) t += red_raw[(long)wv * ldr + c];
-                   return t;
-               },
-               [&](int c, float t) { dgamma[c] += t; });
+    const float4* const sets[1] = {acc};
+    wave_cols_reduce<1, NW, LN_MAXV>(red_raw, sets, C, ws, [&](int, int c, float t) { dgamma[c] += t; });
 }
 // LayerScale backward feeding a Linear backward directly: dy = gamma * dout is never written in fp32 - the kernel emits
 // what the weight / input gradient GEMMs of the preceding Linear consume, dy16 [R][C] and dy16T [C][ldt] (zero padded
@@ -695,7 +623,6 @@ __global__ __launch_bounds__(1024) void lsres_bwd16_kernel(const float* __restri
         const int c = lane + 64 * i;
         g[i] = c < C4 ? g4[c] : make_float4(0, 0, 0, 0);
     }
-    typedef __bf16 bf16x4r_t __attribute__((ext_vector_type(4)));
     const long ntiles = (ldt + 63) / 64;
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long r0 = tile * 64;
@@ -715,8 +642,7 @@ __global__ __launch_bounds__(1024) void lsres_bwd16_kernel(const float* __restri
                     if (rv) {
                         d = dr[c];
                         if (y_f16) {          // y saved as IEEE fp16 by the producing GEMM's epilogue: it only enters the gamma gradient
-                            typedef _Float16 ls_h4_t __attribute__((ext_vector_type(4)));
-                            const ls_h4_t h = __builtin_bit_cast(ls_h4_t, yh[c]);
+                            const f16x4_t h = __builtin_bit_cast(f16x4_t, yh[c]);
                             yv = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
                         } else yv = yr[c];
                     }
@@ -726,12 +652,10 @@ __global__ __launch_bounds__(1024) void lsres_bwd16_kernel(const float* __restri
                         spe_drop_scale4(seed, offset, (uint64_t)(rv ? row : 0) * (uint64_t)C + 4u * (unsigned)c, p_drop, ks);
                         d.x *= ks[0]; d.y *= ks[1]; d.z *= ks[2]; d.w *= ks[3];
                     }
-                    ag[i].x += d.x * yv.x; ag[i].y += d.y * yv.y; ag[i].z += d.z * yv.z; ag[i].w += d.w * yv.w;
-                    const float4 o = make_float4(d.x * g[i].x, d.y * g[i].y, d.z * g[i].z, d.w * g[i].w);
-                    ab[i].x += o.x; ab[i].y += o.y; ab[i].z += o.z; ab[i].w += o.w;
-                    bf16x4r_t h;
-                    h[0] = (__bf16)o.x; h[1] = (__bf16)o.y; h[2] = (__bf16)o.z; h[3] = (__bf16)o.w;
-                    const uint2 u = __builtin_bit_cast(uint2, h);
+                    spe_fma4(ag[i], d, yv);
+                    const float4 o = spe_mul4(d, g[i]);
+                    ab[i] = spe_add4(ab[i], o);
+                    const uint2 u = spe_pack_bf16x4(o);
                     if (rv && dy16) *reinterpret_cast<uint2*>(dy16 + row * C + 4 * c) = u;
                     *reinterpret_cast<uint2*>(lsT + rl * ldl + 4 * c) = u;        // rows past R stage zeros
                 }
@@ -754,34 +678,47 @@ __global__ __launch_bounds__(1024) void lsres_bwd16_kernel(const float* __restri
         }
         __syncthreads();
     }
-    // column sums of the 16 waves through LDS, then across the workgroups in a fixed order (det_reduce.h)
-    float* red = reinterpret_cast<float*>(lsT);
-    const int ldr = C + 4;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C4) {
-            *reinterpret_cast<float4*>(red + (long)w * ldr + 4 * c) = ag[i];
-            *reinterpret_cast<float4*>(red + (long)(16 + w) * ldr + 4 * c) = ab[i];
-        }
-    }
-    __syncthreads();
-    det_reduce(ws, 0, blockIdx.x, gridDim.x, 2 * C, threadIdx.x, 1024,
-               [&](int c) {
-                   const int k = c >= C, cc = k ? c - C : c;
-                   float t = 0.f;
-#pragma unroll
-                   for (int wv = 0; wv < 16; ++wv) t += red[(long)(16 * k + wv) * ldr + cc];
-                   return t;
-               },
-               [&](int c, float t) { float* dst = (c >= C) ? db : dgamma; if (dst) dst[c >= C ? c - C : c] += t; });
+    // dgamma / db += total; the tile's LDS (every wave is past the barrier that ends the tile loop) holds the per-wave sums
+    const float4* const sets[2] = {ag, ab};
+    wave_cols_reduce<2, 16, MAXV>(reinterpret_cast<float*>(lsT), sets, C, ws, [&](int k, int c, float t) {
+        float* dst = k ? db : dgamma;
+        if (dst) dst[c] += t;
+    });
 }
 
-// C-ABI: see include/spe_hip.h (spe_layerscale_residual_bwd16).  -2: C % 4 != 0, C > 1024, ldt not a multiple of 64
-// or smaller than R, misaligned pointers.
 static int lsres_bwd16_launch(const float* dout, const void* y, int y_f16, const float* gamma, void* dy16, void* dy16T, long ldt,
                               float* db, float* dgamma, long R, int C, float p_drop, uint64_t seed, uint64_t offset, const float* sscale, long rps,
-                              hipStream_t st);
+                              hipStream_t st) {
+    if (R <= 0) return 0;
+    if ((C & 3) || C > 256 * LN_MAXV || (ldt & 63) || ldt < R) return -2;
+    if ((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gamma) |
+         reinterpret_cast<uintptr_t>(dy16) | reinterpret_cast<uintptr_t>(dy16T)) & 15) return -2;
+    const int tile_bytes = 64 * (C + 8) * 2, red_bytes = 32 * (C + 4) * 4;
+    const int smem = tile_bytes > red_bytes ? tile_bytes : red_bytes;
+    // 2 float4 per lane up to C = 512: fewer live registers per wave than the 4 the widest rows need
+    const int variant = C <= 512 ? 0 : 1;
+    const auto kernel = variant == 0 ? lsres_bwd16_kernel<2> : lsres_bwd16_kernel<LN_MAXV>;
+    static bool attr[2] = {false, false};
+    if (!attr[variant]) {
+        constexpr int mx = 64 * (256 * LN_MAXV + 8) * 2 > 32 * (256 * LN_MAXV + 4) * 4 ? 64 * (256 * LN_MAXV + 8) * 2 : 32 * (256 * LN_MAXV + 4) * 4;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+        if (e != hipSuccess) return (int)e;
+        attr[variant] = true;
+    }
+    long nb = (ldt + 63) / 64; if (nb > 256) nb = 256;
+    DetWs ws = spe_detws();
+    const DetDeferSeg sg[2] = {{dgamma, C}, {db, C}};
+    float* region = det_defer_try(1, nb, 2 * C, 2, sg, st);        // deferred: dgamma / db += totals at the next flush
+    if (region) ws.defer = region; else DET_CHECK(ws, 1, nb, 2 * C);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(1024), smem, st, dout, reinterpret_cast<const float*>(y), gamma,
+                       reinterpret_cast<unsigned short*>(dy16), reinterpret_cast<unsigned short*>(dy16T), ldt, db, dgamma, R, C, ws, y_f16,
+                       p_drop, seed, offset, sscale, rps);
+    if (region) det_defer_commit(region, 1, nb, 2 * C, 2, sg, 1);
+    SPE_CHECK_LAUNCH();
+    return 0;
+}
+// C-ABI: see include/spe_hip.h (spe_layerscale_residual_bwd16).  -2: C % 4 != 0, C > 1024, ldt not a multiple of 64
+// or smaller than R, misaligned pointers.
 extern "C" int spe_layerscale_residual_bwd16(const float* dout, const void* y, int y_f16, const float* gamma, void* dy16, void* dy16T, long ldt,
                                              float* db, float* dgamma, long R, int C, hipStream_t st) {
     return lsres_bwd16_launch(dout, y, y_f16, gamma, dy16, dy16T, ldt, db, dgamma, R, C, 0.f, 0, 0, nullptr, 1, st);
@@ -793,39 +730,6 @@ extern "C" int spe_layerscale_residual_bwd16d(const float* dout, const void* y, 
     if (p_drop < 0.f || p_drop >= 1.f || (sample_scale && rows_per_sample <= 0)) return -2;
     return lsres_bwd16_launch(dout, y, y_f16, gamma, dy16, dy16T, ldt, db, dgamma, R, C, p_drop, seed, offset, sample_scale,
                               sample_scale ? rows_per_sample : 1, st);
-}
-static int lsres_bwd16_launch(const float* dout, const void* y, int y_f16, const float* gamma, void* dy16, void* dy16T, long ldt,
-                              float* db, float* dgamma, long R, int C, float p_drop, uint64_t seed, uint64_t offset, const float* sscale, long rps,
-                              hipStream_t st) {
-    if (R <= 0) return 0;
-    if ((C & 3) || C > 256 * LN_MAXV || (ldt & 63) || ldt < R) return -2;
-    if ((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gamma) |
-         reinterpret_cast<uintptr_t>(dy16) | reinterpret_cast<uintptr_t>(dy16T)) & 15) return -2;
-    const int tile_bytes = 64 * (C + 8) * 2, red_bytes = 32 * (C + 4) * 4;
-    const int smem = tile_bytes > red_bytes ? tile_bytes : red_bytes;
-    static bool attr = false;
-    if (!attr) {
-        constexpr int mx = 64 * (256 * LN_MAXV + 8) * 2 > 32 * (256 * LN_MAXV + 4) * 4 ? 64 * (256 * LN_MAXV + 8) * 2 : 32 * (256 * LN_MAXV + 4) * 4;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lsres_bwd16_kernel<LN_MAXV>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lsres_bwd16_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        if (e != hipSuccess) return (int)e;
-        attr = true;
-    }
-    long nb = (ldt + 63) / 64; if (nb > 256) nb = 256;
-    DetWs ws = spe_detws();
-    const DetDeferSeg sg[2] = {{dgamma, C}, {db, C}};
-    float* region = det_defer_try(1, nb, 2 * C, 2, sg, st);        // deferred: dgamma / db += totals at the next flush
-    if (region) ws.defer = region; else DET_CHECK(ws, 1, nb, 2 * C);
-    // (2 float4 per lane up to C = 512: fewer live registers per wave than the 4 the widest rows need)
-    if (C <= 512) hipLaunchKernelGGL(lsres_bwd16_kernel<2>, dim3((unsigned)nb), dim3(1024), smem, st, dout, reinterpret_cast<const float*>(y), gamma,
-                                     reinterpret_cast<unsigned short*>(dy16), reinterpret_cast<unsigned short*>(dy16T), ldt, db, dgamma, R, C, ws, y_f16,
-                                     p_drop, seed, offset, sscale, rps);
-    else hipLaunchKernelGGL(lsres_bwd16_kernel<LN_MAXV>, dim3((unsigned)nb), dim3(1024), smem, st, dout, reinterpret_cast<const float*>(y), gamma,
-                            reinterpret_cast<unsigned short*>(dy16), reinterpret_cast<unsigned short*>(dy16T), ldt, db, dgamma, R, C, ws, y_f16,
-                            p_drop, seed, offset, sscale, rps);
-    if (region) det_defer_commit(region, 1, nb, 2 * C, 2, sg, 1);
-    SPE_CHECK_LAUNCH();
-    return 0;
 }
 
 extern "C" int spe_layerscale_residual_fwd(const float* x, const float* y, const float* gamma, const float* sample_scale,

@@ -158,6 +158,22 @@ def test_forward_16bit_copies_bit_exact(dev, C, R):
         assert none is None and torch.equal(_bits(y3), _bits(y)) and torch.equal(_bits(y16c), _bits(y16))
 
 
+@pytest.mark.parametrize("p", [0.0, 0.1])
+@pytest.mark.parametrize("R,C", [(1, 4), (5, 192), (3, 1020), (1001, 1024)])
+def test_res_forward_is_plain_forward_of_its_sum(dev, R, C, p):
+    """norm(x + dropout(z)) runs the row body of the plain forward: y, mean and rstd are, bit for bit, what spe_layernorm_fwd makes
+    of the kernel's own `sum`, and without dropout `sum` is torch's fp32 x + z.  Wave-per-row widths only (C = 1024 is a multiple of
+    128 but above 512): a width the plain forward hands to the half-wave kernel is reduced by another tree there."""
+    from spe_amd import kernels as K
+    x, z, gamma, beta = _plain(R, C, dev, 41 * R + C, n_rc=2)
+    eps = 1e-5
+    y, sm, mean, rstd = K.layernorm_res_fwd(x, z, gamma, beta, eps, p, 29, 5)
+    if p == 0:
+        assert torch.equal(_bits(sm), _bits(x + z))
+    for name, got, want in zip(("y", "mean", "rstd"), (y, mean, rstd), K.layernorm_fwd(sm, gamma, beta, eps)):
+        assert torch.equal(_bits(got), _bits(want)), (name, R, C, p)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # backward
 # ------------------------------------------------------------------------------------------------------------------------------
