@@ -259,7 +259,10 @@ int spe_talking_softmax_bwd(const float* dPd, const float* P, const float* S, co
  *   bl[g] log2(e) - M + log2(IL), zero for the rows N .. Np-1 (the addend that turns Wl S into log2 P).  Np: multiple of 16, >= 16 ceil(N / 16).
  * spe_talking_wgrad_reduce: column sums of ws_w (nwg rows of 2*(H*H+H) = [dWl|dbl|dWw|dbw]) STORED (not accumulated) into the four gradient
  *   buffers in fixed order; a NULL destination is skipped.
- * Supported: H in {4,8}, head dim <= 64 and the LDS bound below.  Returns -2 otherwise (use the materialised path: spe_talking_softmax_*). */
+ * Supported: H in {4,8}, head dim <= 64 and the LDS bounds below.  Returns -2 otherwise (use the materialised path: spe_talking_softmax_*).
+ * spe_talking_fused_supported: 1 when the whole composition above runs for (H, head dim) - both are in the kernels' dispatch and the flash
+ *   forward and the two backward kernels fit the LDS with attention dropout on - else 0 (an answer, not a status). */
+int spe_talking_fused_supported(int H, int dh);
 int spe_attn_pack(const float* x, long sb, long sn, long sh, int B, int N, int H, int dh, float scale,
                   void* out, spe_stream_t stream);
 int spe_talking_stats_plan(int B, int N, int nwg, int* steps_per_wg, int* nwg_used);
@@ -281,7 +284,7 @@ int spe_talking_wgrad_reduce(const float* ws_w, int nwg, int H, float* dWl, floa
  *   operand of the output projection.  keepbits (p_drop > 0 and a backward will follow): uint32 [B][nt][nt][64] - the dropout keep flags of
  *   every 16 x 16 tile (bit hp * 8 + 2 r + e of lane l: query l & 15, key 4 (l >> 4) + r, head 2 hp + e); the backward kernels LOAD them
  *   (one dword per lane and tile) instead of regenerating the masks.
- * Supported: H in {4, 8}, 13 * H * ceil(dh / 16) * 512 + 3072 bytes of LDS <= 160 KB; -2 otherwise. */
+ * Supported: H in {4, 8}, 13 * H * ceil(dh / 16) * 512 bytes of LDS (5 stage buffers + 8 resident tiles) <= 160 KB; -2 otherwise. */
 int spe_talking_flash_plan(int B, int N, int nwg, int* steps_per_wg, int* nwg_used, int* nmajor, int* rows_padded);
 int spe_talking_flash_fwd(const void* Qf, const void* Kf, const void* V16, const float* Wl, const float* Ww, const float* bw,
                           const float* c0, int Np, float* ws, float* O, void* O16, void* O16lo, void* keepbits, int B, int H, int N, int dh,

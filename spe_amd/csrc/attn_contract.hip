@@ -1,5 +1,5 @@
-// Streaming contractions of the bf16 score tensors written by the fused talking-heads kernels
-// (attn_fused.hip modes 1 and 3) with a [N, dh] operand:
+// Streaming contractions of the 16-bit blocked score tensors of the talking-heads attention (the dS blocks written by the
+// query-major backward kernel, attn_flash_bwd.hip) with a [N, dh] operand:
 //   trans = 0 :  out[q, :]   = alpha * sum_key T[q, key] X[key, :]     (O = P'd V ; dQ = scale dS K)
 //   trans = 1 :  out[key, :] = alpha * sum_q   T[q, key] X[q, :]       (dV = P'd^T dO ; dK = scale dS^T Q)
 // Reference: the `attn @ v` of models/cait.py:388 and the autograd of cait.py:377-388.
@@ -408,9 +408,9 @@ __global__ __launch_bounds__(256) void attn_pack_rec_kernel(PackJobs a) {
         const bool rv = row < N;
         const float* src = jb.x + b * jb.sb + (long)min(row, N - 1) * jb.sn + h * jb.sh;
         if (lay == 0 || lay == 2) {
-            const int notail = lay == 2;
-            const int rem = dh % 32, full = notail ? (dh + 31) / 32 : dh / 32 + (rem > 16 ? 1 : 0), tail = (!notail && rem > 0 && rem <= 16) ? 1 : 0;
-            uint2* orec = reinterpret_cast<uint2*>(jb.out) + rec * (full * 128 + tail * 64);
+            const FragGeom fg = frag_geom(dh, lay == 2);
+            const int full = fg.full, tail = fg.tail;
+            uint2* orec = reinterpret_cast<uint2*>(jb.out) + rec * fg.rec8;
             for (int st = 0; st < full; ++st) {
                 const int d0 = st * 32 + g * 8;
                 float f[8];

@@ -37,14 +37,13 @@ struct FlashFwdArgs {
 // counters at cfg2: matrix pipe 53 % + vector 46 % busy = no overlap).  So the two wave groups place their ONE barrier per step at
 // different points of the same instruction stream - waves 0-3 in front of H1, waves 4-7 in front of H2 - which holds the groups
 // half a step apart: between two barriers group 0 runs H1(k), H2(k) and group 1 H2(k), H1(k + 1).  Three K buffers, two V buffers.
-#define FLF_NW 8
-#define FLF_MAJ 8                        // q-tiles per workgroup
+#define FLF_NW 8                         // waves per workgroup; FLF_MAJ (q-tiles per workgroup): attn_flash_common.h, with the LDS budget
 #define FLF_HB 4                         // heads per operand-fragment batch of the K Q^T products
 #define FLF_QS (FLF_MAJ / FLF_NW)
 
 template <int H, int DSTEPS, bool TAIL16, bool DROP>
 __global__ __launch_bounds__(64 * FLF_NW, FLF_NW / 4) void talking_flash_fwd_kernel(FlashFwdArgs a) {
-    constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0), DT = 2 * FULL + (TAIL16 ? 1 : 0), REC = DT * 512;
+    constexpr int FULL = FragDims<DSTEPS, TAIL16>::FULL, DT = FragDims<DSTEPS, TAIL16>::DT, REC = FragDims<DSTEPS, TAIL16>::REC;
     constexpr int NW = FLF_NW, QS = FLF_QS;
     constexpr int TILEB = H * REC;                 // one operand, one 16-row tile, all heads
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];           // [K 0][K 1][K 2][V 0][V 1][8 resident tiles x TILEB]
@@ -324,28 +323,11 @@ __global__ __launch_bounds__(256) void flash_merge_kernel(const float* __restric
 }
 
 template <int H, int DSTEPS, bool TAIL16>
-static int launch_flash_fwd(const FlashFwdArgs& a, int nwg, bool drop, hipStream_t st) {
-    constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0), DT = 2 * FULL + (TAIL16 ? 1 : 0), REC = DT * 512;
-    constexpr int smem = (5 + FLF_MAJ) * H * REC;
-    if (smem > 160 * 1024) return -2;              // H * head dim too large for the resident tiles + the stage buffers: use the materialising path
-    static bool attr_set[2] = {false, false};
-    const void* fn = drop ? reinterpret_cast<const void*>(&talking_flash_fwd_kernel<H, DSTEPS, TAIL16, true>)
-                          : reinterpret_cast<const void*>(&talking_flash_fwd_kernel<H, DSTEPS, TAIL16, false>);
-    if (!attr_set[drop]) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_set[drop] = true;
-    }
-    if (drop) hipLaunchKernelGGL((talking_flash_fwd_kernel<H, DSTEPS, TAIL16, true>), dim3(nwg), dim3(64 * FLF_NW), smem, st, a);
-    else hipLaunchKernelGGL((talking_flash_fwd_kernel<H, DSTEPS, TAIL16, false>), dim3(nwg), dim3(64 * FLF_NW), smem, st, a);
-    SPE_CHECK_LAUNCH();
-    return 0;
-}
-
-static inline int flash_dsteps(int dh, int* tail) {
-    const int rem = dh % 32, full = dh / 32 + (rem > 16 ? 1 : 0);
-    *tail = (rem > 0 && rem <= 16) ? 1 : 0;
-    return full + *tail;
+static int launch_flash_fwd(const FlashFwdArgs& a, int nwg, bool drop, hipStream_t st) {       // LDS: flf_lds_bytes (attn_flash_common.h)
+    constexpr int DT = FragDims<DSTEPS, TAIL16>::DT;
+    if constexpr (flf_lds_bytes(H, DT, true) > FL_LDS_MAX) return -2;
+    else return fl_launch<FlashFwdArgs, talking_flash_fwd_kernel<H, DSTEPS, TAIL16, true>, talking_flash_fwd_kernel<H, DSTEPS, TAIL16, false>>(
+        a, nwg, 64 * FLF_NW, flf_lds_bytes(H, DT, false), flf_lds_bytes(H, DT, true), drop, st);
 }
 
 // C-ABI: see include/spe_hip.h
@@ -364,7 +346,6 @@ extern "C" int spe_talking_flash_fwd(const void* Qf, const void* Kf, const void*
     const int nt = (N + 15) / 16;
     if ((long)B * nt <= 0) return 0;
     if (dh < 1 || dh > 64 || nwg <= 0 || (O16lo && !O16) || Np < nt * 16 + 64) return -2;
-    int tail; const int ds = flash_dsteps(dh, &tail);
     const FlashPlan p = fl_plan(B, nt, FLF_MAJ, nt, nwg);
     FlashFwdArgs a;
     a.Qf = (const unsigned char*)Qf; a.Kf = (const unsigned char*)Kf; a.V16 = (const unsigned char*)V16;
@@ -372,16 +353,10 @@ extern "C" int spe_talking_flash_fwd(const void* Qf, const void* Kf, const void*
     a.B = B; a.N = N; a.nt = nt; a.nmaj = p.nmaj; a.spw = p.spw; a.total = p.total;
     a.p_drop = p_drop; a.seed = seed; a.offset = offset; a.keepbits = reinterpret_cast<unsigned*>(p_drop > 0.f ? keepbits : nullptr);
     const bool drop = p_drop > 0.f;
-    int rc = -2;
-#define SPE_FLASH_FWD(HH)                                                                   \
-    if (H == HH && ds == 2 && tail) rc = launch_flash_fwd<HH, 2, true>(a, p.nwg, drop, st);       \
-    else if (H == HH && ds == 2 && !tail) rc = launch_flash_fwd<HH, 2, false>(a, p.nwg, drop, st); \
-    else if (H == HH && ds == 1 && tail) rc = launch_flash_fwd<HH, 1, true>(a, p.nwg, drop, st);  \
-    else if (H == HH && ds == 1 && !tail) rc = launch_flash_fwd<HH, 1, false>(a, p.nwg, drop, st);
-    SPE_FLASH_FWD(8) else SPE_FLASH_FWD(4)
-#undef SPE_FLASH_FWD
+    const int rc = attn_dispatch(H, dh, [&](auto h, auto ds, auto tl) {
+        return launch_flash_fwd<decltype(h)::value, decltype(ds)::value, decltype(tl)::value>(a, p.nwg, drop, st); });
     if (rc != 0) return rc;
-    const int DT = (dh + 15) / 16;
+    const int DT = frag_geom(dh).dt;
     const long nvec = (long)B * p.nmaj * FLF_MAJ * H * DT * 64;
     hipLaunchKernelGGL(flash_merge_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, st, ws, O, (long)N * H * dh, (long)H * dh, (long)dh,
                        reinterpret_cast<unsigned short*>(O16), reinterpret_cast<unsigned short*>(O16lo), B, H, N, nt, dh, DT, p.nmaj, p.spw, nvec);

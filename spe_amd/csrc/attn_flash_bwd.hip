@@ -26,7 +26,6 @@
 // sched_group_barrier interleave requests, the back half first in source order, a query-major pass 1): profiles/HISTORY_r05.md.
 // Timing ablations (-DSPE_ABLATE builds only, tools/ab.py): FLB_DBG_SAMETILE (every workgroup streams tile 0: all L2 hits), FLB_DBG_NOST (no dS store).
 #include "attn_flash_common.h"
-#include <type_traits>
 
 #define FLB_NW 4                         // waves per workgroup = resident tiles per workgroup (one wave per SIMD)
 #define FLB_HB 4                         // heads per operand batch of the score products
@@ -130,7 +129,7 @@ __device__ __forceinline__ void flb_acc_fence(f32x4_t& a) { asm volatile("s_nop 
 
 template <int H, int DSTEPS, bool TAIL16, bool DROP>
 __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdArgs a) {
-    constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0), DT = 2 * FULL + (TAIL16 ? 1 : 0), REC = DT * 512;
+    constexpr int FULL = FragDims<DSTEPS, TAIL16>::FULL, DT = FragDims<DSTEPS, TAIL16>::DT, REC = FragDims<DSTEPS, TAIL16>::REC;
     constexpr int NW = FLB_NW, HB = (H >= FLB_HB) ? FLB_HB : H;
     constexpr int TILEB = H * REC;                  // one operand, one 16-row tile, all heads
     constexpr int KVB = 2 * TILEB;                  // a K / V stage: K fragments, V fragments
@@ -757,7 +756,7 @@ FLB_SCORE_RS_ASM(flb_score_rs_bf16, "v_mfma_f32_16x16x32_bf16", "v_mfma_f32_16x1
 
 template <int H, int DSTEPS, bool TAIL16, bool DROP>
 __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKArgs a) {
-    constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0), DT = 2 * FULL + (TAIL16 ? 1 : 0), REC = DT * 512;
+    constexpr int FULL = FragDims<DSTEPS, TAIL16>::FULL, DT = FragDims<DSTEPS, TAIL16>::DT, REC = FragDims<DSTEPS, TAIL16>::REC;
     constexpr int NW = FLB_NW, HB = (H >= FLB_HB) ? FLB_HB : H;
     constexpr int TILEB = H * REC;                  // one operand, one 16-row tile, all heads
     constexpr int STG = 2 * TILEB;                  // a stage: Q fragments, dO fragments
@@ -1230,44 +1229,24 @@ __global__ __launch_bounds__(256) void bwdk_rows_merge_kernel(const float* __res
     out[i] = acc;
 }
 
-static inline int flb_dsteps(int dh, int* tail) {
-    const int rem = dh % 32, full = dh / 32 + (rem > 16 ? 1 : 0);
-    *tail = (rem > 0 && rem <= 16) ? 1 : 0;
-    return full + *tail;
+// LDS of a workgroup of the query-major kernel: two stages of the two streamed 32-wide tiles, FLB_NK16 slots of the 16-wide tile (each H records of
+// DT * 512 B), the constants, the weight-gradient transpose tiles of the FLB_NW waves and - with dropout - two stages of keep-flag records
+constexpr int flbq_lds_bytes(int H, int DT, bool drop) {
+    return (4 + FLB_NK16) * H * DT * 512 + 512 + FLB_NW * 3 * 4 * H * FLB_GWR + (drop ? 2048 : 0);
 }
-
-template <int H, int DSTEPS, bool TAIL16>
-static int launch_bwdq(const FlashBwdArgs& a, int nwg, bool drop, hipStream_t st) {
-    constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0), DT = 2 * FULL + (TAIL16 ? 1 : 0), REC = DT * 512;
-    constexpr int smem0 = 4 * H * REC + FLB_NK16 * H * REC + 512 + FLB_NW * 3 * 4 * H * FLB_GWR;
-    const int smem = smem0 + (drop ? 2048 : 0);          // + the keep-flag records
-    if (smem > 160 * 1024) return -2;
-    static bool attr_set[2] = {false, false};
-    const void* fn = drop ? reinterpret_cast<const void*>(&talking_bwdq_kernel<H, DSTEPS, TAIL16, true>)
-                          : reinterpret_cast<const void*>(&talking_bwdq_kernel<H, DSTEPS, TAIL16, false>);
-    if (!attr_set[drop]) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_set[drop] = true;
-    }
-    if (drop) hipLaunchKernelGGL((talking_bwdq_kernel<H, DSTEPS, TAIL16, true>), dim3(nwg), dim3(64 * FLB_NW), smem, st, a);
-    else hipLaunchKernelGGL((talking_bwdq_kernel<H, DSTEPS, TAIL16, false>), dim3(nwg), dim3(64 * FLB_NW), smem, st, a);
-    SPE_CHECK_LAUNCH();
-    return 0;
+// ... of the key-major kernel: the same plus two stages of row constants (1 KB each) and of the waves' D rows
+constexpr int flbk_lds_bytes(int H, int DT, bool drop) {
+    return (4 + FLB_NK16) * H * DT * 512 + 2048 + 2 * FLB_NW * 16 * H * 4 + 512 + FLB_NW * 3 * 4 * H * FLB_GWR + (drop ? 2048 : 0);
 }
 
 static int dispatch_bwdq(const FlashBwdArgs& a, int H, int dh, int nwg, hipStream_t st) {
-    int tail; const int ds = flb_dsteps(dh, &tail);
-    const bool drop = a.p_drop > 0.f;
-#define SPE_BWDQ(HH)                                                                       \
-    if (H == HH && ds == 2 && tail) return launch_bwdq<HH, 2, true>(a, nwg, drop, st);     \
-    if (H == HH && ds == 2 && !tail) return launch_bwdq<HH, 2, false>(a, nwg, drop, st);   \
-    if (H == HH && ds == 1 && tail) return launch_bwdq<HH, 1, true>(a, nwg, drop, st);     \
-    if (H == HH && ds == 1 && !tail) return launch_bwdq<HH, 1, false>(a, nwg, drop, st);
-    SPE_BWDQ(8)
-    SPE_BWDQ(4)
-#undef SPE_BWDQ
-    return -2;
+    return attn_dispatch(H, dh, [&](auto h, auto ds, auto tl) {
+        constexpr int HH = decltype(h)::value, DS = decltype(ds)::value, DT = FragDims<DS, decltype(tl)::value>::DT;
+        constexpr bool TL = decltype(tl)::value;
+        if constexpr (flbq_lds_bytes(HH, DT, true) > FL_LDS_MAX) return -2;
+        else return fl_launch<FlashBwdArgs, talking_bwdq_kernel<HH, DS, TL, true>, talking_bwdq_kernel<HH, DS, TL, false>>(
+            a, nwg, 64 * FLB_NW, flbq_lds_bytes(HH, DT, false), flbq_lds_bytes(HH, DT, true), a.p_drop > 0.f, st);
+    });
 }
 
 // C-ABI: see include/spe_hip.h
@@ -1305,7 +1284,7 @@ extern "C" int spe_talking_bwdq_pass2(const void* Qf, const void* dOf, const voi
     a.ws_q = ws_q; a.ws_w = ws_w; a.dS = reinterpret_cast<unsigned short*>(dS); a.Drows = Drows;
     rc = dispatch_bwdq(a, H, dh, p.nwg, st);
     if (rc != 0) return rc;
-    const int DT = (dh + 15) / 16;
+    const int DT = frag_geom(dh).dt;
     const long nvec = (long)B * p.nmaj * FLB_NW * H * DT * 64;
     hipLaunchKernelGGL(bwdq_dq_merge_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, st, ws_q, dq, reinterpret_cast<unsigned short*>(dq16),
                        ob, on, oh, B, H, N, a.nt, dh, DT, p.nmaj, p.spw, scale, nvec);
@@ -1313,39 +1292,23 @@ extern "C" int spe_talking_bwdq_pass2(const void* Qf, const void* dOf, const voi
     return 0;
 }
 
-// ---- key-major pass: launch, dispatch, C-ABI
-template <int H, int DSTEPS, bool TAIL16>
-static int launch_bwdk(const FlashBwdKArgs& a, int nwg, bool drop, hipStream_t st) {
-    constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0), DT = 2 * FULL + (TAIL16 ? 1 : 0), REC = DT * 512;
-    constexpr int smem0 = 4 * H * REC + FLB_NK16 * H * REC + 2048 + 2 * FLB_NW * 16 * H * 4 + 512 + FLB_NW * 3 * 4 * H * FLB_GWR;
-    const int smem = smem0 + (drop ? 2048 : 0);          // + the keep-flag records
-    if (smem > 160 * 1024) return -2;
-    static bool attr_set[2] = {false, false};
-    const void* fn = drop ? reinterpret_cast<const void*>(&talking_bwdk_kernel<H, DSTEPS, TAIL16, true>)
-                          : reinterpret_cast<const void*>(&talking_bwdk_kernel<H, DSTEPS, TAIL16, false>);
-    if (!attr_set[drop]) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_set[drop] = true;
-    }
-    if (drop) hipLaunchKernelGGL((talking_bwdk_kernel<H, DSTEPS, TAIL16, true>), dim3(nwg), dim3(64 * FLB_NW), smem, st, a);
-    else hipLaunchKernelGGL((talking_bwdk_kernel<H, DSTEPS, TAIL16, false>), dim3(nwg), dim3(64 * FLB_NW), smem, st, a);
-    SPE_CHECK_LAUNCH();
-    return 0;
+// ---- key-major pass: dispatch, C-ABI
+static int dispatch_bwdk(const FlashBwdKArgs& a, int H, int dh, int nwg, hipStream_t st) {
+    return attn_dispatch(H, dh, [&](auto h, auto ds, auto tl) {
+        constexpr int HH = decltype(h)::value, DS = decltype(ds)::value, DT = FragDims<DS, decltype(tl)::value>::DT;
+        constexpr bool TL = decltype(tl)::value;
+        if constexpr (flbk_lds_bytes(HH, DT, true) > FL_LDS_MAX) return -2;
+        else return fl_launch<FlashBwdKArgs, talking_bwdk_kernel<HH, DS, TL, true>, talking_bwdk_kernel<HH, DS, TL, false>>(
+            a, nwg, 64 * FLB_NW, flbk_lds_bytes(HH, DT, false), flbk_lds_bytes(HH, DT, true), a.p_drop > 0.f, st);
+    });
 }
 
-static int dispatch_bwdk(const FlashBwdKArgs& a, int H, int dh, int nwg, hipStream_t st) {
-    int tail; const int ds = flb_dsteps(dh, &tail);
-    const bool drop = a.p_drop > 0.f;
-#define SPE_BWDK(HH)                                                                       \
-    if (H == HH && ds == 2 && tail) return launch_bwdk<HH, 2, true>(a, nwg, drop, st);     \
-    if (H == HH && ds == 2 && !tail) return launch_bwdk<HH, 2, false>(a, nwg, drop, st);   \
-    if (H == HH && ds == 1 && tail) return launch_bwdk<HH, 1, true>(a, nwg, drop, st);     \
-    if (H == HH && ds == 1 && !tail) return launch_bwdk<HH, 1, false>(a, nwg, drop, st);
-    SPE_BWDK(8)
-    SPE_BWDK(4)
-#undef SPE_BWDK
-    return -2;
+// C-ABI: see include/spe_hip.h.  1 when (H, head dim) is in the dispatch and the flash forward and both backward kernels fit the LDS with dropout on.
+extern "C" int spe_talking_fused_supported(int H, int dh) {
+    return attn_dispatch(H, dh, [](auto h, auto ds, auto tl) {
+        constexpr int HH = decltype(h)::value, DT = FragDims<decltype(ds)::value, decltype(tl)::value>::DT;
+        return (flf_lds_bytes(HH, DT, true) <= FL_LDS_MAX && flbq_lds_bytes(HH, DT, true) <= FL_LDS_MAX && flbk_lds_bytes(HH, DT, true) <= FL_LDS_MAX) ? 0 : -2;
+    }) == 0;
 }
 
 extern "C" int spe_talking_bwdk_pass1(const void* Qf, const void* dOf, const void* dO16, const void* Kf, const void* Vf, const float* Wl, const float* Ww,
@@ -1367,7 +1330,7 @@ extern "C" int spe_talking_bwdk_pass1(const void* Qf, const void* dOf, const voi
     const long n = (long)B * Np * H;
     hipLaunchKernelGGL(bwdk_rows_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ws_d, Drows, B, H, N, Np, p.nmaj);
     SPE_CHECK_LAUNCH();
-    const int DT = (dh + 15) / 16;
+    const int DT = frag_geom(dh).dt;
     const long nvec = (long)B * p.nmaj * FLB_NW * H * DT * 64;
     hipLaunchKernelGGL(bwdq_dq_merge_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, st, ws_v, dv, reinterpret_cast<unsigned short*>(dv16),
                        ob, on, oh, B, H, N, nt, dh, DT, p.nmaj, p.spw, 1.0f / FL_PD_SCALE, nvec);

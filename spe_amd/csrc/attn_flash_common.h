@@ -1,5 +1,6 @@
-// Shared pieces of the flash-style talking-heads kernels (attn_flash.hip): operand formats, the head mixes on the matrix pipe,
-// the LDS-DMA stage copy and the flattened work split.  Reference: models/cait.py:377-389 (Attention_talking_head.forward).
+// Shared pieces of the talking-heads attention kernels (attn_stats.hip, attn_pmean.hip, attn_flash.hip, attn_flash_bwd.hip): operand formats, the
+// head mixes on the matrix pipe, the fragment loads, the LDS-DMA stage copy, the flattened work split, and the host side every launcher shares -
+// the (H, head dim) dispatch and the launch of a kernel with a dropout variant and dynamic LDS.  Reference: models/cait.py:377-389 (Attention_talking_head.forward).
 //
 // Orientation-free facts the kernels rely on (measured on gfx950, tools/micro/mfma_rates.hip):
 //   * v_mfma_f32_16x16x16_{f16,bf16} issues in 18 cycles per SIMD - the same as v_mfma_f32_16x16x32 with twice the work;
@@ -12,7 +13,8 @@
 // With A := W[4gh + (lane & 3)][..] (a per-lane constant) and B := the lane's own head values, register i of the result is output
 // head 4gh + i of the lane's own element - no data moves between lanes.
 #pragma once
-#include "common.h"
+#include <type_traits>
+#include "attn_pack.h"
 
 typedef unsigned int flu32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int flu32x2_t __attribute__((ext_vector_type(2)));
@@ -144,12 +146,25 @@ __device__ __forceinline__ void fl_glds16_run(const void* sbase, const unsigned*
                      :: "s"(sbase), "s"(lds_dst), "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "n"(STRIDE) : "memory", "scc");
 }
 
-// ---- fragment records (spe_attn_pack_multi): per (b, h, 16-row tile) FULL steps of 64 lanes x 16 B (32 head dims each) and, when
-// TAIL16, one step of 64 lanes x 8 B (16 head dims); the 16-wide "X16" records are DT = 2 FULL + TAIL16 steps of 64 x 8 B.  Both are
-// DT * 512 bytes.  Operands read back from an LDS image of a record:
+// ---- fragment records (attn_pack.h: frag_geom / FragDims).  Operand `st` of record `rec` of a packed tensor in global memory: the tail step's 8-B
+// operands are zero-extended and go through the same 16x16x32 instruction - lane group g then holds k-slots 8g..8g+3 = head dims FULL*32 + 4g..4g+3
+// in BOTH operands and zeros in slots 8g+4..8g+7, so the products line up; the saving of the tail step is its load bytes, the matrix pipe is idle
+// anyway.  Accumulate chains stay within ONE MFMA shape everywhere in this library: a 16x16x16 MFMA whose SrcC is the destination of the 16x16x32
+// MFMA issued right before it gave run-to-run different results on gfx950 as hipcc (ROCm 7.2) schedules it (profiles/HISTORY_r01_r03.md).
+template <int DSTEPS, bool TAIL16>
+__device__ __forceinline__ flu32x4_t fl_frag_global(const flu32x4_t* __restrict__ base, long rec, int st, int lane) {
+    constexpr int FULL = FragDims<DSTEPS, TAIL16>::FULL, REC8 = FragDims<DSTEPS, TAIL16>::REC / 8;
+    const uint2* p = reinterpret_cast<const uint2*>(base) + rec * REC8;
+    if (TAIL16 && st == FULL) {
+        const uint2 v = p[FULL * 128 + lane];
+        return (flu32x4_t){v.x, v.y, 0u, 0u};
+    }
+    return *reinterpret_cast<const flu32x4_t*>(p + st * 128 + lane * 2);
+}
+// the same operand read back from an LDS image of a record
 template <int DSTEPS, bool TAIL16>
 __device__ __forceinline__ flu32x4_t fl_frag_lds(const unsigned char* rec, int st, int lane) {
-    constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0);
+    constexpr int FULL = FragDims<DSTEPS, TAIL16>::FULL;
     if (TAIL16 && st == FULL) {
         const flu32x2_t v = *reinterpret_cast<const flu32x2_t*>(rec + FULL * 1024 + lane * 8);
         return (flu32x4_t){v[0], v[1], 0u, 0u};          // zero-extended: the tail step goes through the same 16x16x32 instruction
@@ -186,7 +201,7 @@ __host__ __device__ static inline FlashPlan fl_plan(int B, int nt_major, int per
     return p;
 }
 
-// ---- dropout keep-scales shared with attn_fused.hip (same counter layout: (b, head pair, query, 4-key group), eight 16-bit lots)
+// ---- dropout keep-scales (counter layout: (b, head pair, query, 4-key group), eight 16-bit lots)
 template <int H>
 __device__ __forceinline__ void fl_keep_lots(uint64_t seed, uint64_t offset, int b, int hp, int q, int key0, int N, uint32_t (&o)[4]) {
     const uint64_t ctr = (((uint64_t)b * (H / 2) + hp) * (uint64_t)N + (uint64_t)q) * (uint64_t)((N + 3) >> 2) + (uint64_t)(key0 >> 2);
@@ -207,3 +222,47 @@ __device__ __forceinline__ uint32_t fl_quad_bcast(uint32_t v, int t) {
         default: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xff, 0xf, 0xf, false);
     }
 }
+
+// ---- host side: ONE (H, head dim) dispatch.  f(integral_constant<int, H>, integral_constant<int, DSTEPS>, bool_constant<TAIL16>) -> status is
+// called for H in {4, 8} and head dim 1 .. 64; -2 (unsupported) otherwise.  A kernel whose LDS need rules a combination out cuts it inside f
+// with `if constexpr`, so that it is not instantiated either.
+template <int H, typename F>
+static int attn_dispatch_h(int dh, F&& f) {
+    const FragGeom g = frag_geom(dh);
+    using HC = std::integral_constant<int, H>;
+    using D1 = std::integral_constant<int, 1>;
+    using D2 = std::integral_constant<int, 2>;
+    if (g.dsteps == 2) return g.tail ? f(HC{}, D2{}, std::true_type{}) : f(HC{}, D2{}, std::false_type{});
+    return g.tail ? f(HC{}, D1{}, std::true_type{}) : f(HC{}, D1{}, std::false_type{});
+}
+template <typename F>
+static int attn_dispatch(int H, int dh, F&& f) {
+    if (dh < 1 || dh > 64) return -2;
+    if (H == 8) return attn_dispatch_h<8>(dh, f);
+    if (H == 4) return attn_dispatch_h<4>(dh, f);
+    return -2;
+}
+
+#define FL_LDS_MAX (160 * 1024)      // bytes of LDS a workgroup can have on gfx950
+// Launch of a kernel with dynamic LDS in its dropout (KDROP) or plain (KPLAIN) instantiation; lds[drop] bytes.  The opt-in to more than 64 KB is
+// made once per instantiation (the statics belong to this template's instantiation, i.e. to the kernel pair), never per launch.
+template <typename Args, void (*KDROP)(Args), void (*KPLAIN)(Args)>
+static int fl_launch(const Args& a, int nwg, int threads, int lds_plain, int lds_drop, bool drop, hipStream_t st) {
+    static bool attr_set[2] = {false, false};
+    void (*const fn)(Args) = drop ? KDROP : KPLAIN;
+    const int smem = drop ? lds_drop : lds_plain;
+    if (!attr_set[drop]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) return (int)e;
+        attr_set[drop] = true;
+    }
+    hipLaunchKernelGGL(fn, dim3(nwg), dim3(threads), smem, st, a);
+    SPE_CHECK_LAUNCH();
+    return 0;
+}
+// LDS of a workgroup of the flash forward (attn_flash.hip; here because spe_talking_fused_supported, next to the backward kernels' budgets in
+// attn_flash_bwd.hip, asks for it too): 3 K + 2 V stage buffers and the FLF_MAJ resident q-tiles, each one tile of all heads (H records of
+// DT * 512 B); the keep flags go straight to global memory, so the dropout variant needs the same.  H = 8 with head dim 49 .. 64 does not fit: it
+// has no instantiation and takes the materialising path.
+#define FLF_MAJ 8                    // q-tiles a workgroup of the flash forward keeps resident
+constexpr int flf_lds_bytes(int H, int DT, bool /*drop*/) { return (5 + FLF_MAJ) * H * DT * 512; }

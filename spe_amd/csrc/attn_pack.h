@@ -1,5 +1,6 @@
-// Shared by attn_fused.hip (spe_attn_pack) and attn_contract.hip (spe_attn_pack_multi): the 16-bit fragment record
-// layout of the fused talking-heads score kernels (see frag_load in attn_fused.hip).
+// The 16-bit fragment record layout of the talking-heads score kernels - its geometry (frag_geom, FragDims: the one statement of the head dim ->
+// record rule) and the pack of one 8-B unit - shared by attn_stats.hip (spe_attn_pack), attn_contract.hip (spe_attn_pack_multi), decoder_kv.hip
+// and, through attn_flash_common.h, by every kernel that reads the records (fl_frag_global there).
 //
 // Element format of a packed tensor: bf16, or IEEE fp16 (`f16` = 1).  The forward operands of the attention - q * scale *
 // log2(e), k, v and the probabilities - are O(1) quantities, far inside fp16's range, and fp16 carries 3 more mantissa bits
@@ -8,6 +9,29 @@
 // fp16 conversions saturate at +-65504 instead of producing infinities.
 #pragma once
 #include "common.h"
+
+// Fragment record of one (b, h, 16-row tile): `full` steps of 32 head dims (64 lanes x 16 B) followed, when `tail`, by one step of 16 dims (64 lanes
+// x 8 B) for a remainder of 1 .. 16 dims.  dh = 48 is 32 + 16: 1.5 KB per record instead of the 2 KB of two padded 32-steps - the score kernels are
+// sensitive to exactly this L2 -> register traffic (measured: dh 32 vs 48-padded-to-64 differ by 0.2 ms per block over the four passes).  The same
+// bytes read as 16-wide "X16" records are dt = 2 full + tail steps of 64 lanes x 8 B.  notail: ceil(dh / 32) full steps and no tail step (the layout
+// of mha_flash.hip).
+struct FragGeom { int full, tail, dsteps, dt, rec8, bytes; };            // rec8 / bytes: record size in 8-B units / in bytes
+__host__ __device__ constexpr FragGeom frag_geom(int dh, bool notail = false) {
+    const int rem = dh % 32, full = notail ? (dh + 31) / 32 : dh / 32 + (rem > 16 ? 1 : 0), tail = (!notail && rem > 0 && rem <= 16) ? 1 : 0;
+    return FragGeom{full, tail, full + tail, 2 * full + tail, full * 128 + tail * 64, full * 1024 + tail * 512};
+}
+constexpr bool frag_geom_is(int dh, bool notail, int full, int tail) {
+    const FragGeom g = frag_geom(dh, notail);
+    return g.full == full && g.tail == tail && g.dsteps == full + tail && g.dt == 2 * full + tail && g.rec8 * 8 == g.bytes && g.bytes == g.dt * 512;
+}
+static_assert(frag_geom_is(8, false, 0, 1) && frag_geom_is(16, false, 0, 1), "head dim 1 .. 16: the tail step alone");
+static_assert(frag_geom_is(17, false, 1, 0) && frag_geom_is(24, false, 1, 0) && frag_geom_is(32, false, 1, 0), "head dim 17 .. 32: one full step");
+static_assert(frag_geom_is(33, false, 1, 1) && frag_geom_is(48, false, 1, 1), "head dim 33 .. 48: full + tail");
+static_assert(frag_geom_is(49, false, 2, 0) && frag_geom_is(64, false, 2, 0), "head dim 49 .. 64: two full steps");
+static_assert(frag_geom_is(48, true, 2, 0) && frag_geom_is(40, true, 2, 0), "notail: full steps only");
+// the same for kernels templated on (DSTEPS = full + tail, TAIL16)
+template <int DSTEPS, bool TAIL16>
+struct FragDims { static constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0), DT = 2 * FULL + (TAIL16 ? 1 : 0), REC = DT * 512; };
 
 __device__ __forceinline__ unsigned short spe_f2h_sat(float f) {
     // v_med3_f32 keeps a NaN (fminf / fmaxf would turn it into +-65504 and hide a diverged run); v_cvt_f16_f32: round to nearest even
@@ -32,9 +56,9 @@ __device__ __forceinline__ uint2 spe_cvt4_16(float a, float b, float c, float d,
 template <typename IT>
 __device__ __forceinline__ void attn_pack_unit_t(const float* __restrict__ x, long sb, long sn, long sh, int N, int H, int dh, int nt,
                                                  float scale, IT i, uint2* __restrict__ out, int notail = 0, int f16 = 0) {
-    // notail: ceil(dh/32) full steps and no 16-wide tail step (the layout of mha_flash.hip)
-    const int rem = dh % 32, full = notail ? (dh + 31) / 32 : dh / 32 + (rem > 16 ? 1 : 0), tail = (!notail && rem > 0 && rem <= 16) ? 1 : 0;
-    const IT rec8 = (IT)(full * 128 + tail * 64);
+    const FragGeom fg = frag_geom(dh, notail != 0);
+    const int full = fg.full;
+    const IT rec8 = (IT)fg.rec8;
     const IT rec = i / rec8; const int u = (int)(i - rec * rec8);
     const IT bh = rec / (IT)nt; const int tile = (int)(rec - bh * (IT)nt);
     const int b = (int)(bh / (IT)H), h = (int)(bh - (IT)b * (IT)H);
@@ -62,7 +86,6 @@ __device__ __forceinline__ void attn_pack_unit(const float* __restrict__ x, long
 
 // 8-B units of a packed tensor [B, H, nt] records
 __host__ __device__ static inline long attn_pack_units(int B, int N, int H, int dh, int notail = 0) {
-    const int nt = (N + 15) / 16, rem = dh % 32, full = notail ? (dh + 31) / 32 : dh / 32 + (rem > 16 ? 1 : 0), tail = (!notail && rem > 0 && rem <= 16) ? 1 : 0;
-    return (long)B * H * nt * (full * 128 + tail * 64);
+    return (long)B * H * ((N + 15) / 16) * frag_geom(dh, notail != 0).rec8;
 }
 

@@ -11,33 +11,12 @@
 // Work: one wave per (b, q-tile, chunk of PM_KT key tiles); each 16 x 16 tile of M is owned by exactly one wave of a launch, which reads, adds
 // and writes it back (plain vector loads and stores, no atomics); the blocks' launches are ordered on the stream - deterministic.
 // spe_attn_pmean_dense is the same accumulation from a materialised P [B, H, N, ld] (the fp32 path: bf16x3, unsupported head geometries).
-#include "common.h"
-
-typedef unsigned int pm_u32x4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 pm_f16x8_t __attribute__((ext_vector_type(8)));
+#include "attn_flash_common.h"
 
 #define PM_KT 8                      // key tiles per wave
 
-// fragment record of one (b, h, 16-row tile): FULL 32-wide steps of [lane][8] then, when TAIL16, one 16-wide step of [lane][4], zero-extended
-// here so that the same 16x16x32 instruction consumes it (the layout of include/spe_hip.h, "Operand format")
-template <int DSTEPS, bool TAIL16>
-__device__ __forceinline__ pm_u32x4_t pm_frag(const pm_u32x4_t* __restrict__ base, long rec, int st, int lane) {
-    constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0);
-    constexpr int REC8 = FULL * 128 + (TAIL16 ? 64 : 0);           // record size in 8-B units
-    const uint2* p = reinterpret_cast<const uint2*>(base) + rec * REC8;
-    if (TAIL16 && st == FULL) {
-        const uint2 v = p[FULL * 128 + lane];
-        return (pm_u32x4_t){v.x, v.y, 0u, 0u};
-    }
-    return *reinterpret_cast<const pm_u32x4_t*>(p + st * 128 + lane * 2);
-}
-
-__device__ __forceinline__ f32x4_t pm_mfma(pm_u32x4_t a, pm_u32x4_t b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(pm_f16x8_t, a), __builtin_bit_cast(pm_f16x8_t, b), c, 0, 0, 0);
-}
-
 template <int H, int DSTEPS, bool TAIL16>
-__global__ __launch_bounds__(256) void attn_pmean_kernel(const pm_u32x4_t* __restrict__ Qf, const pm_u32x4_t* __restrict__ Kf,
+__global__ __launch_bounds__(256) void attn_pmean_kernel(const flu32x4_t* __restrict__ Qf, const flu32x4_t* __restrict__ Kf,
                                                          const float* __restrict__ Wl, const float* __restrict__ c0, int Np, float* __restrict__ M,
                                                          float alpha, int B, int N, int nt, int nkc) {
     const int lane = threadIdx.x & 63;
@@ -46,18 +25,15 @@ __global__ __launch_bounds__(256) void attn_pmean_kernel(const pm_u32x4_t* __res
     const int kc = (int)(wid % nkc), qt = (int)((wid / nkc) % nt), b = (int)(wid / ((long)nkc * nt));
     // S^T = K Q^T (M = keys, N = queries): lane = (query qt * 16 + (lane & 15), keys 4 (lane >> 4) + r of the key tile)
     const int q = qt * 16 + (lane & 15);
-    pm_u32x4_t qreg[H * DSTEPS];
+    flu32x4_t qreg[H * DSTEPS];
 #pragma unroll
     for (int h = 0; h < H; ++h)
 #pragma unroll
-        for (int st = 0; st < DSTEPS; ++st) qreg[h * DSTEPS + st] = pm_frag<DSTEPS, TAIL16>(Qf, ((long)b * H + h) * nt + qt, st, lane);
+        for (int st = 0; st < DSTEPS; ++st) qreg[h * DSTEPS + st] = fl_frag_global<DSTEPS, TAIL16>(Qf, ((long)b * H + h) * nt + qt, st, lane);
     // the fp32 Wl mix on v_mfma_f32_4x4x1_16b_f32 (attn_stats.hip, mix_keys_f32): register i of a lane accumulates output head 4 gh + i of the
     // lane's own (query, key) element; it starts from that head's row constant
     float A[H / 4][H];
-#pragma unroll
-    for (int gh = 0; gh < H / 4; ++gh)
-#pragma unroll
-        for (int h = 0; h < H; ++h) A[gh][h] = Wl[(4 * gh + (lane & 3)) * H + h];
+    fl_mixA_f32<H, false>(Wl, lane, A);
     f32x4_t cq[H / 4];                                            // rows N .. Np - 1 of c0 are zero: q < nt * 16 <= Np
 #pragma unroll
     for (int gh = 0; gh < H / 4; ++gh) cq[gh] = *reinterpret_cast<const f32x4_t*>(c0 + ((long)b * Np + q) * H + 4 * gh);
@@ -69,7 +45,7 @@ __global__ __launch_bounds__(256) void attn_pmean_kernel(const pm_u32x4_t* __res
         for (int h = 0; h < H; ++h) {
             f32x4_t c = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int st = 0; st < DSTEPS; ++st) c = pm_mfma(pm_frag<DSTEPS, TAIL16>(Kf, ((long)b * H + h) * nt + kt, st, lane), qreg[h * DSTEPS + st], c);
+            for (int st = 0; st < DSTEPS; ++st) c = fl_mfma32<true>(fl_frag_global<DSTEPS, TAIL16>(Kf, ((long)b * H + h) * nt + kt, st, lane), qreg[h * DSTEPS + st], c);
             s[h] = c;
         }
         f32x4_t sp[4][H / 4];
@@ -125,23 +101,17 @@ extern "C" int spe_attn_pmean(const void* Qf, const void* Kf, const float* Wl, c
     const int nt = (N + 15) / 16;
     if ((long)B * nt <= 0) return 0;
     if (dh < 1 || dh > 64 || Np < nt * 16) return -2;
-    const int rem = dh % 32, full = dh / 32 + (rem > 16 ? 1 : 0), tail = (rem > 0 && rem <= 16) ? 1 : 0;
-    const int ds = full + tail;
     const int nkc = (nt + PM_KT - 1) / PM_KT;
     const long waves = (long)B * nt * nkc;
     const dim3 grid((unsigned)((waves + 3) / 4));
-    const pm_u32x4_t* q4 = reinterpret_cast<const pm_u32x4_t*>(Qf);
-    const pm_u32x4_t* k4 = reinterpret_cast<const pm_u32x4_t*>(Kf);
-#define SPE_PMEAN_GO(HH, DS, TL)                                                                                                  \
-    if (H == HH && ds == DS && tail == TL) {                                                                                      \
-        hipLaunchKernelGGL((attn_pmean_kernel<HH, DS, (TL != 0)>), grid, dim3(256), 0, st, q4, k4, Wl, c0, Np, M, alpha, B, N, nt, nkc); \
-        SPE_CHECK_LAUNCH();                                                                                                       \
-        return 0;                                                                                                                 \
-    }
-    SPE_PMEAN_GO(8, 2, 1) SPE_PMEAN_GO(8, 2, 0) SPE_PMEAN_GO(8, 1, 1) SPE_PMEAN_GO(8, 1, 0)
-    SPE_PMEAN_GO(4, 2, 1) SPE_PMEAN_GO(4, 2, 0) SPE_PMEAN_GO(4, 1, 1) SPE_PMEAN_GO(4, 1, 0)
-#undef SPE_PMEAN_GO
-    return -2;
+    const flu32x4_t* q4 = reinterpret_cast<const flu32x4_t*>(Qf);
+    const flu32x4_t* k4 = reinterpret_cast<const flu32x4_t*>(Kf);
+    return attn_dispatch(H, dh, [&](auto h, auto ds, auto tl) {
+        hipLaunchKernelGGL((attn_pmean_kernel<decltype(h)::value, decltype(ds)::value, decltype(tl)::value>), grid, dim3(256), 0, st, q4, k4, Wl, c0, Np, M,
+                           alpha, B, N, nt, nkc);
+        SPE_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int spe_attn_pmean_dense(const float* P, float* M, float alpha, int B, int H, int N, long ld, hipStream_t st) {

@@ -19,14 +19,10 @@
 // workgroup's range covers 1-3 q-tile pairs ("segments"): waves (0, 1) work on q-tile 2p, waves (2, 3) on q-tile 2p + 1, both pairs walk the same
 // key tiles in step (the second request of a K fragment is served by the vector L1).  Per-segment row statistics go to a workspace indexed by
 // (q-tile, slot = workgroup - first workgroup of the q-tile) and are merged by spe_attn_merge_rows.
-#include "common.h"
-#include "attn_pack.h"
-
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8m_t __attribute__((ext_vector_type(8)));
+#include "attn_flash_common.h"
 
 struct StatsArgs {
-    const u32x4_t* Qf; const u32x4_t* Kf;
+    const flu32x4_t* Qf; const flu32x4_t* Kf;
     const float* Wl; const float* bl;
     float* ws_stats;                                      // partial row stats [B*nt][MAXSLOT][H][16][2]
     int B, N, nt;                                         // nt = ceil(N/16) tiles per axis
@@ -47,7 +43,6 @@ __host__ __device__ __forceinline__ int fused_nch(int nt) { return (nt >= 16 * F
 __host__ __device__ __forceinline__ int fused_kbeg(int c, int nt, int nch) { return (int)((long)c * nt / nch); }
 
 #define EXP2(x) __builtin_amdgcn_exp2f(x)
-#define SPE_LOG2E 1.4426950408889634f
 
 // The softmax-input mix S' = Wl S + bl on the matrix pipe IN FP32: v_mfma_f32_4x4x1_16b_f32 computes, in each of its 16 blocks of
 // 4 lanes, the outer product D[i][j] += A[i] B[j] with D[i][.] in register i of lane 4b + j (probed on gfx950:
@@ -56,14 +51,7 @@ __host__ __device__ __forceinline__ int fused_kbeg(int c, int nt, int nch) { ret
 // contribution to output heads 4gh .. 4gh+3 of the lane's own (query, key) element: H * H/4 instructions per key are the whole
 // H x H mix, bit-for-bit the fmaf chain the packed FMAs computed (an f32 MFMA is a k-ordered fmaf chain) at the same
 // FLOP rate (64 / clk / SIMD) - but on the pipe that is ~10 % busy instead of the one that bounds these kernels.  Measured
-// (cfg2, isolated): removing the packed-FMA mix altogether is worth 0.049 of the statistics pass' 0.176 ms.
-template <int H>
-__device__ __forceinline__ void mixA4_build(const float* __restrict__ W, int lane, float (&A)[H / 4][H]) {
-#pragma unroll
-    for (int gh = 0; gh < H / 4; ++gh)
-#pragma unroll
-        for (int h = 0; h < H; ++h) A[gh][h] = W[(4 * gh + (lane & 3)) * H + h];
-}
+// (cfg2, isolated): removing the packed-FMA mix altogether is worth 0.049 of the statistics pass' 0.176 ms.  A: fl_mixA_f32 (attn_flash_common.h).
 // out[r][gh][i] = c[4gh + i] + sum_h W[4gh + i][h] s[h][r]   (r: the lane's 4 keys)
 template <int H>
 __device__ __forceinline__ void mix_keys_f32(const f32x4_t (&s)[H], const float (&A)[H / 4][H], const float (&c)[H], f32x4_t (&out)[4][H / 4]) {
@@ -79,39 +67,16 @@ __device__ __forceinline__ void mix_keys_f32(const f32x4_t (&s)[H], const float 
             for (int gh = 0; gh < H / 4; ++gh) out[r][gh] = __builtin_amdgcn_mfma_f32_4x4x1f32(A[gh][h], s[h][r], out[r][gh], 0, 0, 0);
 }
 
-// Fragment record of one (b, h, 16-row tile): FULL = DSTEPS - TAIL16 steps of 32 head dims (64 lanes x 16 B) followed,
-// when TAIL16, by one step of 16 dims (64 lanes x 8 B: the v_mfma_f32_16x16x16_bf16 operand).  dh = 48 is 32 + 16:
-// 1.5 KB per record instead of the 2 KB of two padded 32-steps - the score kernels are sensitive to exactly this
-// L2 -> register traffic (measured: dh 32 vs 48-padded-to-64 differ by 0.2 ms per block over the four passes).
-template <int DSTEPS, bool TAIL16>
-__device__ __forceinline__ u32x4_t frag_load(const u32x4_t* __restrict__ base, long rec, int st, int lane) {
-    constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0);
-    constexpr int REC8 = FULL * 128 + (TAIL16 ? 64 : 0);           // record size in 8-B units
-    const uint2* p = reinterpret_cast<const uint2*>(base) + rec * REC8;
-    if (TAIL16 && st == FULL) {
-        const uint2 v = p[FULL * 128 + lane];
-        return (u32x4_t){v.x, v.y, 0u, 0u};
-    }
-    return *reinterpret_cast<const u32x4_t*>(p + st * 128 + lane * 2);
-}
-// The tail step's 8-B operands are zero-extended (frag_load) and go through the same 16x16x32 instruction: lane group
-// g then holds k-slots 8g..8g+3 = head dims FULL*32 + 4g..4g+3 in BOTH operands and zeros in slots 8g+4..8g+7, so the
-// products line up - the saving of the tail step is its load bytes, the matrix pipe is idle anyway.
-// Accumulate chains stay within ONE MFMA shape everywhere in this library: a 16x16x16 MFMA whose SrcC is the destination of the 16x16x32 MFMA issued
-// right before it gave run-to-run different results on gfx950 as hipcc (ROCm 7.2) schedules it (profiles/HISTORY_r01_r03.md).
-__device__ __forceinline__ f32x4_t frag_mfma(u32x4_t a, u32x4_t b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8m_t, a), __builtin_bit_cast(f16x8m_t, b), c, 0, 0, 0);
-}
-// same record, addressed as (uniform byte pointer of the (b, h) row of records) + (32-bit byte offset of the tile's record): the
+// The record of fl_frag_global (attn_flash_common.h), addressed as (uniform byte pointer of the (b, h) row of records) + (32-bit byte offset of the tile's record): the
 // row pointers are computed once per segment, so a fragment costs no 64-bit address arithmetic in the tile loop
 template <int DSTEPS, bool TAIL16>
-__device__ __forceinline__ u32x4_t frag_load_row(const char* __restrict__ row, unsigned recoff, int st, int lane) {
-    constexpr int FULL = DSTEPS - (TAIL16 ? 1 : 0);
+__device__ __forceinline__ flu32x4_t frag_load_row(const char* __restrict__ row, unsigned recoff, int st, int lane) {
+    constexpr int FULL = FragDims<DSTEPS, TAIL16>::FULL;
     if (TAIL16 && st == FULL) {
         const uint2 v = *reinterpret_cast<const uint2*>(row + (recoff + (unsigned)(FULL * 1024) + (unsigned)lane * 8u));
-        return (u32x4_t){v.x, v.y, 0u, 0u};
+        return (flu32x4_t){v.x, v.y, 0u, 0u};
     }
-    return *reinterpret_cast<const u32x4_t*>(row + (recoff + (unsigned)(st * 1024) + (unsigned)lane * 16u));
+    return *reinterpret_cast<const flu32x4_t*>(row + (recoff + (unsigned)(st * 1024) + (unsigned)lane * 16u));
 }
 
 template <int H, int DSTEPS, bool TAIL16, int KT>
@@ -136,9 +101,9 @@ __global__ __launch_bounds__(256, 2) void talking_stats_kernel(StatsArgs a) {
     // Scores arrive in the log2 domain (the pack folds scale * log2(e) into the Q fragments): Wl S + bl*log2(e) is log2(e) * S'
     float vbl2[H];
 #pragma unroll
-    for (int g = 0; g < H; ++g) vbl2[g] = a.bl[g] * SPE_LOG2E;
+    for (int g = 0; g < H; ++g) vbl2[g] = a.bl[g] * FL_LOG2E;
     float Al4[H / 4][H];                                   // f32 operand of the S' mix (see mix_keys_f32)
-    mixA4_build<H>(a.Wl, lane, Al4);
+    fl_mixA_f32<H, false>(a.Wl, lane, Al4);
 
     long s = s_begin;
     while (s < s_end) {
@@ -149,10 +114,10 @@ __global__ __launch_bounds__(256, 2) void talking_stats_kernel(StatsArgs a) {
         const bool qt_valid = qt_own < nt;
         const int qt = qt_valid ? qt_own : nt - 1;
         // ---- the q-tile's Q fragments live in registers for the whole segment (64 VGPRs at H = 8, dh <= 64)
-        u32x4_t qreg[NFR];
+        flu32x4_t qreg[NFR];
         __syncthreads();                                       // sred of the previous segment has been consumed
 #pragma unroll
-        for (int f = 0; f < NFR; ++f) qreg[f] = frag_load<DSTEPS, TAIL16>(a.Qf, ((long)b * H + f / DSTEPS) * nt + qt, f % DSTEPS, lane);
+        for (int f = 0; f < NFR; ++f) qreg[f] = fl_frag_global<DSTEPS, TAIL16>(a.Qf, ((long)b * H + f / DSTEPS) * nt + qt, f % DSTEPS, lane);
         // ---- per-lane row state
         float rm[H], rl[H];
 #pragma unroll
@@ -160,8 +125,8 @@ __global__ __launch_bounds__(256, 2) void talking_stats_kernel(StatsArgs a) {
 
         // A wave's unit of work is a macro step of KT consecutive 16-key tiles against the 16 queries of the q-tile.  Waves of a q-tile take
         // macro steps round-robin.  Operand-fragment staging registers for one batch of H head jobs, and the batch loader:
-        u32x4_t fr[H * DSTEPS];
-        constexpr unsigned RECB = (unsigned)((DSTEPS - (TAIL16 ? 1 : 0)) * 1024 + (TAIL16 ? 512 : 0));   // bytes per fragment record
+        flu32x4_t fr[H * DSTEPS];
+        constexpr unsigned RECB = (unsigned)FragDims<DSTEPS, TAIL16>::REC;   // bytes per fragment record
         const char* krow[H];
 #pragma unroll
         for (int h = 0; h < H; ++h) krow[h] = reinterpret_cast<const char*>(a.Kf) + ((long)b * H + h) * nt * (long)RECB;
@@ -189,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void talking_stats_kernel(StatsArgs a) {
 #pragma unroll
                     for (int st = 0; st < DSTEPS; ++st)
 #pragma unroll
-                        for (int jj = 0; jj < QG; ++jj) c[jj] = frag_mfma(fr[(g0 + jj) * DSTEPS + st], qreg[(g0 + jj) * DSTEPS + st], c[jj]);
+                        for (int jj = 0; jj < QG; ++jj) c[jj] = fl_mfma32<true>(fr[(g0 + jj) * DSTEPS + st], qreg[(g0 + jj) * DSTEPS + st], c[jj]);
 #pragma unroll
                     for (int jj = 0; jj < QG; ++jj) acc[tj][g0 + jj] = c[jj];
                 }
@@ -308,10 +273,10 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(const float* __restrict
         }
     const float il = 1.f / l;
     out0[o] = mn; out1[o] = il;
-    rows[((long)b * Np + q) * H + g] = bl[g] * SPE_LOG2E - mn + __builtin_amdgcn_logf(il);
+    rows[((long)b * Np + q) * H + g] = bl[g] * FL_LOG2E - mn + __builtin_amdgcn_logf(il);
 }
 
-// Pack rows of x[b][n][h][d] (strides sb, sn, sh; unit d stride) into bf16 fragment records (see frag_load):
+// Pack rows of x[b][n][h][d] (strides sb, sn, sh; unit d stride) into bf16 fragment records (attn_pack.h):
 // per (b, h, tile): FULL steps of [lane][8] = scale * x[tile*16 + (lane&15)][st*32 + (lane>>4)*8 + i], then (tail) one
 // step of [lane][4] = scale * x[tile*16 + (lane&15)][FULL*32 + (lane>>4)*4 + i]; 0 outside N x dh.  One thread per 8-B unit.
 __global__ __launch_bounds__(256) void attn_pack_kernel(const float* __restrict__ x, long sb, long sn, long sh, int B, int N, int H,
@@ -391,25 +356,16 @@ static void make_plan(int B, int nt, int nwg, int* spw_out, int* nwg_out) {
 extern "C" int spe_talking_stats(const void* Qf, const void* Kf, const float* Wl, const float* bl, float* ws_stats,
                                  int B, int H, int N, int dh, int nwg, hipStream_t st) {
     StatsArgs a;
-    a.Qf = (const u32x4_t*)Qf; a.Kf = (const u32x4_t*)Kf; a.Wl = Wl; a.bl = bl; a.ws_stats = ws_stats;
+    a.Qf = (const flu32x4_t*)Qf; a.Kf = (const flu32x4_t*)Kf; a.Wl = Wl; a.bl = bl; a.ws_stats = ws_stats;
     a.B = B; a.N = N; a.nt = (N + 15) / 16;
     if ((long)B * a.nt * a.nt <= 0) return 0;
     make_plan(B, a.nt, nwg, &a.steps_per_wg, &nwg);
-    // head dim -> d-steps: full 32-wide steps, plus a 16-wide tail step when the remainder is 1..16
-    const int rem = dh % 32, full = dh / 32 + (rem > 16 ? 1 : 0), tail = (rem > 0 && rem <= 16) ? 1 : 0;
-    const int ds = full + tail;
-    if (dh < 1 || dh > 64) return -2;
     // macro step = 1 key tile (4 tiles measured slower inside the step: occupancy)
-#define SPE_STATS_GO(HH, DS, TL)                                                                                        \
-    if (H == HH && ds == DS && tail == TL) {                                                                            \
-        hipLaunchKernelGGL((talking_stats_kernel<HH, DS, (TL != 0), 1>), dim3(nwg), dim3(256), 0, st, a);              \
-        SPE_CHECK_LAUNCH();                                                                                             \
-        return 0;                                                                                                       \
-    }
-    SPE_STATS_GO(8, 2, 1) SPE_STATS_GO(8, 2, 0) SPE_STATS_GO(8, 1, 1) SPE_STATS_GO(8, 1, 0)
-    SPE_STATS_GO(4, 2, 1) SPE_STATS_GO(4, 2, 0) SPE_STATS_GO(4, 1, 1) SPE_STATS_GO(4, 1, 0)
-#undef SPE_STATS_GO
-    return -2;
+    return attn_dispatch(H, dh, [&](auto h, auto ds, auto tl) {
+        hipLaunchKernelGGL((talking_stats_kernel<decltype(h)::value, decltype(ds)::value, decltype(tl)::value, 1>), dim3(nwg), dim3(256), 0, st, a);
+        SPE_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 // steps_per_wg the launcher will use for (B, N, nwg): callers size the statistics workspace with it.

@@ -29,7 +29,7 @@ struct GemmArgs {
     int kt_per_split;
     int vecA, vecB;
     int xcd_bind;  // 0: plain tile order, 1: M-panels bound to XCDs, 2: N-panels bound to XCDs
-    int a_bf16;    // A operand is stored as bf16 (the transposed score tensors of attn_fused.hip)
+    int a_bf16;    // A operand is stored as bf16 (spe_gemm_ex: a 16-bit tensor such as a transposed score tensor)
 };
 
 // ---- HBM -> registers -------------------------------------------------------------------

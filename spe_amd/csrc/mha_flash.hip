@@ -5,7 +5,7 @@
 // writing the [B,H,Lq,Lk] score tensor (the materialising path moves 4 such fp32 tensors per layer: 53 MB each for
 // the decoder's 200 x 4150 cross-attention, 1.1 GB each for an encoder layer at N = 4150).
 //
-// Element formats as in attn_fused.hip: the FORWARD operands - q * scale * log2(e), k (Qf, Kf), v (V16) and the probabilities of
+// Element formats as in the talking-heads kernels (attn_pack.h, attn_flash.hip): the FORWARD operands - q * scale * log2(e), k (Qf, Kf), v (V16) and the probabilities of
 // the P.V product - are O(1) and go through fp16 (3 more mantissa bits than bf16, same size and MFMA rate: the bf16 version of
 // this kernel alone cost 1.1e-3 of pred_logits at cfg2, tools/error_budget.py); the backward recomputes S from the same fp16
 // fragments and keeps bf16 wherever a gradient is an operand (Vf.dOf, P^T dO16, dS K16, dS^T Q16).

@@ -1206,11 +1206,12 @@ def get_cu_reserve():
     return _CU_RESERVE
 
 
+@_functools.lru_cache(maxsize=None)
 def fused_supported(H, dh):
-    """The fused attention path = statistics pass + flash forward + the two backward kernels: all of them must fit (LDS: the 8 resident tiles + 5
-    stage buffers of the forward, the stage buffers + transpose tiles of the backward kernels).  H = 8 with head dim 49 .. 64 does not (no model
-    of the reference has it: every CaiT variant uses head dim 48); it takes the materialised path."""
-    return flash_supported(H, dh) and bwdq_supported(H, dh) and bwdk_supported(H, dh)
+    """The fused attention path = statistics pass + flash forward + the two backward kernels: (H, head dim) must be in their dispatch and all of
+    them must fit the LDS - the library's answer, from the budgets its launchers use (spe_talking_fused_supported).  H = 8 with head dim 49 .. 64
+    does not fit (no model of the reference has it: every CaiT variant uses head dim 48); it takes the materialised path."""
+    return bool(lib.load().spe_talking_fused_supported(H, dh))
 
 
 LOG2E = 1.4426950408889634
@@ -1229,9 +1230,8 @@ def attn_pack(x4, scale=1.0):
 _PLANS = {}          # work splits are pure functions of (shape, workgroup budget): asked once per shape, not once per block and step
 
 
-def fused_plan(B, N, mode=0):
+def fused_plan(B, N):
     """(steps per workgroup, workgroups) the statistics pass uses (parametrises attn_merge_rows)."""
-    assert mode == 0
     key = ("stats", B, N, STATS_NWG)
     r = _PLANS.get(key)
     if r is None:
@@ -1241,9 +1241,12 @@ def fused_plan(B, N, mode=0):
     return r
 
 
+STATS_SLOTS = 8        # workgroups whose partials one q-tile's statistics may come from (FUSED_MAXSLOT of csrc/attn_stats.hip)
+
+
 def talking_stats(Qf, Kf, Wl, bl, ws_stats, B, H, N, dh):
-    """Statistics pass: partial (max, sum) of softmax_k(Wl S + bl) per (b, head, query) -> ws_stats (B * nt * 8 * H * 32 floats); merged by
-    attn_merge_rows with fused_plan(B, N)[0]."""
+    """Statistics pass: partial (max, sum) of softmax_k(Wl S + bl) per (b, head, query) -> ws_stats (B * nt * STATS_SLOTS * H * 16 * 2 floats);
+    merged by attn_merge_rows with fused_plan(B, N)[0]."""
     _call("spe_talking_stats", _p(Qf), _p(Kf), _p(Wl), _p(bl), _p(ws_stats), B, H, N, dh, STATS_NWG, _st())
 
 
@@ -1265,7 +1268,7 @@ def attn_pack16(x4):
 
 def frag_record_elems(dh):
     """bf16 elements of one (b, h, 16-row tile) fragment record of the score kernels: full 32-wide d-steps of 64 x 8
-    plus a 16-wide tail step of 64 x 4 when dh % 32 is in 1..16 (csrc/attn_stats.hip: frag_load)."""
+    plus a 16-wide tail step of 64 x 4 when dh % 32 is in 1..16 (csrc/attn_pack.h: frag_geom)."""
     rem = dh % 32
     full = dh // 32 + (1 if rem > 16 else 0)
     return full * 512 + (256 if 0 < rem <= 16 else 0)
@@ -1383,11 +1386,6 @@ FLASH_NWG = 256
 FLASH_SLOTS = 8
 
 
-def flash_supported(H, dh):
-    """The flash kernels keep 8 resident tiles and 5 stage buffers (+ 3 KB of row constants) in LDS."""
-    return H in (4, 8) and dh <= 64 and 13 * H * ((dh + 15) // 16) * 512 + 3072 <= 160 * 1024
-
-
 def flash_plan(B, N):
     """(steps per workgroup, workgroups, major tile groups per image, padded rows of the row-constant arrays)."""
     key = ("flash", B, N, FLASH_NWG)
@@ -1430,11 +1428,6 @@ def talking_flash_fwd(Qf, Kf, V16, Wl, Ww, bw, c0, B, H, N, dh, p_drop, seed, of
 
 
 # ---- the two backward kernels (csrc/attn_flash_bwd.hip): 4-wave workgroups, one wave per SIMD, one workgroup per CU
-def bwdq_supported(H, dh):
-    DT = (dh + 15) // 16
-    return H in (4, 8) and dh <= 64 and 7 * H * DT * 512 + 512 + 4 * 3 * 4 * H * 144 <= 160 * 1024
-
-
 def bwdq_plan(B, N):
     """(steps per workgroup, workgroups, major (4 q-tile) groups per image) of the q-major backward passes."""
     budget = max(8, FLASH_NWG - _CU_RESERVE)
@@ -1447,11 +1440,6 @@ def bwdq_plan(B, N):
             _PLANS.clear()
         r = _PLANS[key] = (spw.value, nwg.value, nmaj.value)
     return r
-
-
-def bwdk_supported(H, dh):
-    DT = (dh + 15) // 16
-    return H in (4, 8) and dh <= 64 and 7 * H * DT * 512 + 2048 + 2 * 4 * 16 * H * 4 + 512 + 4 * 3 * 4 * H * 144 <= 160 * 1024
 
 
 def talking_bwdk_pass1(Qf, dOf, dO16, Kf, Vf, Wl, Ww, bw, c0, keepbits, dv4, dv16, B, H, N, dh, p_drop):
@@ -1492,6 +1480,13 @@ def attn_merge_rows(ws_stats, bl, B, H, N, spw):
     c0 = torch.empty((B, Np, H), device=ws_stats.device, dtype=torch.float32)
     _call("spe_attn_merge_rows", _p(ws_stats), _p(M), _p(IL), _p(bl), _p(c0), Np, B, H, N, spw, _st())
     return M, IL, c0
+
+
+def talking_row_constants(Qf, Kf, Wl, bl, B, H, N, dh):
+    """Statistics pass + merge -> (M, IL [B,H,N], c0 [B,Np,H]): what the flash forward, the head-mean and the backward kernels need of the softmax."""
+    ws_stats = torch.empty((B * ((N + 15) // 16) * STATS_SLOTS * H * 16 * 2,), device=Qf.device, dtype=torch.float32)
+    talking_stats(Qf, Kf, Wl, bl, ws_stats, B, H, N, dh)
+    return attn_merge_rows(ws_stats, bl, B, H, N, fused_plan(B, N)[0])
 
 
 def attn_pmean(Qf, Kf, Wl, c0, M, alpha, B, H, N, dh):

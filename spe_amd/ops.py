@@ -511,7 +511,6 @@ class _TalkingHeadsAttentionFused(Function):
         v5 = qkv.view(B, N, 3, H, dh)
         q, k, v = v5[:, :, 0], v5[:, :, 1], v5[:, :, 2]
         nt = (N + 15) // 16
-        spw0, _ = K.fused_plan(B, N)
         # the fused kernels work in the log2 domain: scale * log2(e) is folded into the Q fragments
         # forward operands in fp16 (O(1) values: 3 more mantissa bits than bf16 at the same size and MFMA rate)
         # ... and, when a backward will follow, its bf16 fragments of q / k / v from the same read of qkv (one launch; the fp32
@@ -522,11 +521,9 @@ class _TalkingHeadsAttentionFused(Function):
         packed = K.attn_pack_multi(jobs)
         Qf, Kf, V16 = packed[:3]
         Wl, bl, Ww, bw = Wl.contiguous(), bl.contiguous(), Ww.contiguous(), bw.contiguous()
-        ws_stats = torch.empty((B * nt * 8 * H * 32,), device=qkv.device, dtype=torch.float32)
         seed, off = K.next_rng() if p_drop > 0 else (0, 0)
-        K.talking_stats(Qf, Kf, Wl, bl, ws_stats, B, H, N, dh)
+        _, _, c0 = K.talking_row_constants(Qf, Kf, Wl, bl, B, H, N, dh)
         want16 = K.produces16(B * N, C)
-        _, _, c0 = K.attn_merge_rows(ws_stats, bl, B, H, N, spw0)
         if acc is not None:
             K.attn_pmean(Qf, Kf, Wl, c0, acc[0], acc[1], B, H, N, dh)
         # P' goes from the head mix straight into the P' V products: nothing N x N is stored or saved - the backward recomputes it

@@ -254,3 +254,18 @@ def test_accuracy_and_postprocess_refine_multi():
                 labs += [c] * len(keep); scs.append(prob[b, keep, c]); bxs.append(boxes[b, keep])
         assert res[b]["labels"].tolist() == labs
         assert torch.equal(res[b]["scores"], torch.cat(scs)) and torch.equal(res[b]["boxes"], torch.cat(bxs))
+
+
+def test_fused_attention_support_and_record_size_match_the_stated_rules():
+    """kernels.fused_supported is the library's answer (spe_talking_fused_supported: the dispatch of the attention kernels and the LDS budgets their
+    launchers use); here it is held against the rule written out - H in {4, 8}, head dim <= 64, and at H = 8 at most 48 (the resident tiles and
+    stage buffers of head dim 49 .. 64 at 8 heads exceed the 160 KB of LDS).  frag_record_elems (the Python side's record size, 2-byte elements)
+    is held against the C rule restated: full 32-wide steps of 1 KB plus a 16-wide tail step of 512 B for a remainder of 1 .. 16."""
+    from spe_amd import kernels as K
+    for H in (1, 2, 4, 8, 12, 16):
+        for dh in range(1, 97):
+            assert K.fused_supported(H, dh) == (H in (4, 8) and dh <= 64 and (H == 4 or dh <= 48)), (H, dh)
+    for dh in range(1, 65):
+        rem = dh % 32
+        full, tail = dh // 32 + (rem > 16), 0 < rem <= 16
+        assert K.frag_record_elems(dh) * 2 == full * 1024 + tail * 512, dh

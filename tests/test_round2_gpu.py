@@ -299,12 +299,8 @@ def test_fused_attention_with_dropout(dev, H, N, dh, B, p):
         from test_round6_gpu import _keep_from_bits
         v5 = qkv.detach().view(B, N, 3, H, dh)
         Qf, Kf, V16 = K.attn_pack_multi([(v5[:, :, 0], scale * K.LOG2E, 32 + K.F16), (v5[:, :, 1], 1.0, 32 + K.F16), (v5[:, :, 2], 1.0, 16 + K.F16)])
-        nt = (N + 15) // 16
-        spw0, _ = K.fused_plan(B, N)
-        ws = torch.empty((B * nt * 8 * H * 32,), device=dev)
         args = [t.detach().contiguous() for t in (Wl, bl, Ww, bw)]
-        K.talking_stats(Qf, Kf, args[0], args[1], ws, B, H, N, dh)
-        _, _, c0 = K.attn_merge_rows(ws, args[1], B, H, N, spw0)
+        _, _, c0 = K.talking_row_constants(Qf, Kf, args[0], args[1], B, H, N, dh)
         bits = K.talking_flash_fwd(Qf, Kf, V16, args[0], args[2], args[3], c0, B, H, N, dh, p, seed, off, want_bits=True)[3]
         keepm = _keep_from_bits(bits, H, N)
         rate = 1.0 - float(keepm.float().mean())
@@ -854,7 +850,8 @@ def test_nms_known_answers(dev):
 # round 4: flash-style talking-heads forward (csrc/attn_flash.hip) - no N x N tensor in HBM
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,H,N,dh,p", [(1, 4, 12, 8, 0.0), (2, 4, 35, 8, 0.1), (2, 4, 196, 48, 0.0), (1, 8, 130, 48, 0.1),
-                                        (2, 8, 1100, 48, 0.0), (1, 4, 300, 32, 0.05), (1, 4, 257, 64, 0.0), (1, 4, 77, 24, 0.1)])
+                                        (2, 8, 1100, 48, 0.0), (1, 4, 300, 32, 0.05), (1, 4, 257, 64, 0.0), (1, 4, 77, 24, 0.1),
+                                        (1, 8, 100, 16, 0.1), (1, 8, 100, 32, 0.0)])
 def test_flash_forward_vs_fp64(dev, B, H, N, dh, p):
     """spe_talking_stats + spe_attn_merge_rows + spe_talking_flash_fwd against the fp64 restatement of reference models/cait.py:377-389 evaluated on
     the operands as the kernels see them (q scale log2 e, k, v rounded to fp16), with the dropout mask decoded from the stored keep flags: what
@@ -870,11 +867,7 @@ def test_flash_forward_vs_fp64(dev, B, H, N, dh, p):
     scale = dh ** -0.5
     v5 = qkv.view(B, N, 3, H, dh)
     Qf, Kf, V16 = K.attn_pack_multi([(v5[:, :, 0], scale * K.LOG2E, 32 + K.F16), (v5[:, :, 1], 1.0, 32 + K.F16), (v5[:, :, 2], 1.0, 16 + K.F16)])
-    nt = (N + 15) // 16
-    spw0, _ = K.fused_plan(B, N)
-    ws = torch.zeros(B * nt * 8 * H * 32, device=dev)
-    K.talking_stats(Qf, Kf, Wl, bl, ws, B, H, N, dh)
-    M, IL, c0 = K.attn_merge_rows(ws, bl, B, H, N, spw0)
+    M, IL, c0 = K.talking_row_constants(Qf, Kf, Wl, bl, B, H, N, dh)
     O, O16, O16lo, bits = K.talking_flash_fwd(Qf, Kf, V16, Wl, Ww, bw, c0, B, H, N, dh, p, 11, 5, True, True, want_bits=True)
     O2, _, _ = K.talking_flash_fwd(Qf, Kf, V16, Wl, Ww, bw, c0, B, H, N, dh, p, 11, 5)
     assert torch.isfinite(O).all()
@@ -895,3 +888,24 @@ def test_flash_forward_vs_fp64(dev, B, H, N, dh, p):
     print(f"[flash forward vs fp64 B={B} H={H} N={N} dh={dh} p={p}] {err:.2e}")
     assert err < 6e-4, err
     assert float((O16.float().view_as(O) + O16lo.float().view_as(O) - O).abs().max()) <= 2e-5 * float(O.abs().max())
+
+
+@pytest.mark.gpu
+def test_flash_forward_rejects_unsupported_shape(dev):
+    """H = 8 with head dim 64 is outside the fused path (the resident tiles and stage buffers do not fit the LDS): spe_talking_flash_fwd answers -2
+    from its argument checks and launches nothing - the partial-result workspace, which the kernel and its merge would write, keeps its fill."""
+    from spe_amd import kernels as K
+    from spe_amd.lib import SpeLibraryError
+    B, H, N, dh = 1, 8, 100, 64
+    assert not K.fused_supported(H, dh)
+    g = torch.Generator().manual_seed(5)
+    v5 = torch.randn(B, N, 3, H, dh, generator=g).to(dev)
+    Qf, Kf, V16 = K.attn_pack_multi([(v5[:, :, 0], 1.0, 32 + K.F16), (v5[:, :, 1], 1.0, 32 + K.F16), (v5[:, :, 2], 1.0, 16 + K.F16)])
+    W, b = torch.eye(H, device=dev), torch.zeros(H, device=dev)
+    c0 = torch.zeros((B, K.flash_plan(B, N)[3], H), device=dev)
+    ws = K._flash_ws(dev, B * K.flash_plan(B, N)[2] * K.FLASH_SLOTS * 128 * H * 16 * ((dh + 15) // 16))
+    ws.fill_(-7.0)
+    with pytest.raises(SpeLibraryError, match="status -2"):
+        K.talking_flash_fwd(Qf, Kf, V16, W, W, b, c0, B, H, N, dh, 0.0, 0, 0)
+    torch.cuda.synchronize()
+    assert (ws == -7.0).all()

@@ -57,11 +57,7 @@ def _run_kernels(B, H, N, dh, p_drop, dev, seed=1):
     Qf, Kf, V16, Vf, K16 = K.attn_pack_multi([(q, scale * K.LOG2E, 32 + K.F16), (k, 1.0, 32 + K.F16), (v, 1.0, 16 + K.F16), (v, 1.0, 32), (k, 1.0, 16)])
     dO4 = dO.view(B, N, H, dh)
     dOf, dO16 = K.attn_pack_multi([(dO4, 1.0, 32), (dO4, 1.0, 16)])
-    nt = (N + 15) // 16
-    spw0, _ = K.fused_plan(B, N, 0)
-    ws = torch.zeros(B * nt * 8 * H * 32, device=dev)
-    K.talking_stats(Qf, Kf, Wl, bl, ws, B, H, N, dh)
-    M, IL, c0 = K.attn_merge_rows(ws, bl, B, H, N, spw0)
+    M, IL, c0 = K.talking_row_constants(Qf, Kf, Wl, bl, B, H, N, dh)
     bits = K.talking_flash_fwd(Qf, Kf, V16, Wl, Ww, bw, c0, B, H, N, dh, p_drop, 7, 3, want_bits=True)[3] if p_drop > 0 else None
 
     def run():
@@ -119,7 +115,7 @@ def _fp64_backward(x, b, H, N, p_drop):
 
 CASES = [(2, 8, 4150, 48, 0.0), (2, 8, 4150, 48, 0.05), (1, 8, 6200, 48, 0.0), (1, 8, 6200, 48, 0.1),
          (1, 8, 100, 48, 0.0), (2, 4, 196, 48, 0.0), (2, 8, 1100, 48, 0.1), (1, 4, 300, 32, 0.05), (2, 8, 400, 16, 0.0), (1, 8, 2070, 48, 0.0),
-         (1, 4, 64, 64, 0.2)]
+         (1, 4, 64, 64, 0.2), (1, 8, 100, 32, 0.1), (1, 4, 100, 16, 0.0)]
 
 
 @pytest.mark.parametrize("B,H,N,dh,p_drop", CASES)
@@ -192,10 +188,7 @@ def test_attention_node_has_one_backward_composition(dev):
     with torch.no_grad():
         v5 = qkv.detach().view(B, N, 3, H, dh)
         Qf, Kf, V16 = K.attn_pack_multi([(v5[:, :, 0], dh ** -0.5 * K.LOG2E, 32 + K.F16), (v5[:, :, 1], 1.0, 32 + K.F16), (v5[:, :, 2], 1.0, 16 + K.F16)])
-        nt = (N + 15) // 16
-        ws = torch.zeros(B * nt * 8 * H * 32, device=dev)
-        K.talking_stats(Qf, Kf, Wl.detach(), bl.detach(), ws, B, H, N, dh)
-        _, _, c0 = K.attn_merge_rows(ws, bl.detach(), B, H, N, K.fused_plan(B, N, 0)[0])
+        _, _, c0 = K.talking_row_constants(Qf, Kf, Wl.detach(), bl.detach(), B, H, N, dh)
         bits = K.talking_flash_fwd(Qf, Kf, V16, Wl.detach(), Ww.detach(), bw.detach(), c0, B, H, N, dh, p, 31, 1, want_bits=True)[3]
         keep = _keep_from_bits(bits, H, N).double() / (1.0 - p)
     dd = [t.detach().double().requires_grad_() for t in (qkv, Wl, bl, Ww, bw)]

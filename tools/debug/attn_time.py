@@ -31,9 +31,6 @@ q, k, v = v5[:, :, 0], v5[:, :, 1], v5[:, :, 2]
 Qf, Kf, V16, Vf, K16, Q16 = K.attn_pack_multi([(q, scale * K.LOG2E, 32 + K.F16), (k, 1.0, 32 + K.F16), (v, 1.0, 16 + K.F16), (v, 1.0, 32), (k, 1.0, 16), (q, 1.0, 16)])
 dO4 = dO.view(B, N, H, dh)
 dOf, dO16 = K.attn_pack_multi([(dO4, 1.0, 32), (dO4, 1.0, 16)])
-nt = (N + 15) // 16
-spw0, _ = K.fused_plan(B, N)
-ws = torch.zeros(B * nt * 8 * H * 32, device=dev)
 dqkv = torch.empty(B, N, 3 * C, device=dev, dtype=torch.bfloat16)
 d5 = dqkv.view(B, N, 3, H, dh)
 dS = K.score_blocks(B, H, N, dev)
@@ -41,8 +38,7 @@ state = {}
 
 
 def stats():
-    K.talking_stats(Qf, Kf, Wl, bl, ws, B, H, N, dh)
-    state["c0"] = K.attn_merge_rows(ws, bl, B, H, N, spw0)[2]
+    state["c0"] = K.talking_row_constants(Qf, Kf, Wl, bl, B, H, N, dh)[2]
 
 
 def fwd():
@@ -61,7 +57,7 @@ def dk():
     K.attn_contract(dS, Q16, None, True, alpha=scale, out16=d5[:, :, 1])
 
 
-steps = [("statistics + merge", stats), ("flash forward + merge", fwd), ("key-major backward (D, dWw, dbw, dV) + merges", bwdk),
+steps = [("statistics + merge (workspace allocated per call)", stats), ("flash forward + merge", fwd), ("key-major backward (D, dWw, dbw, dV) + merges", bwdk),
          ("query-major backward (dS, dWl, dbl, dQ) + merge", bwdq), ("dK contraction", dk)]
 for _, f in steps:
     f()

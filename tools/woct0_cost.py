@@ -53,10 +53,7 @@ def pmean_cost(dev, B, H, N, dh):
     bl = 0.1 * torch.randn(H, device=dev)
     q, k = qkv.view(B, N, 3, H, dh)[:, :, 0], qkv.view(B, N, 3, H, dh)[:, :, 1]
     Qf, Kf = K.attn_pack_multi([(q, dh ** -0.5 * K.LOG2E, 32 + K.F16), (k, 1.0, 32 + K.F16)])
-    nt = (N + 15) // 16
-    ws = torch.empty((B * nt * 8 * H * 32,), device=dev)
-    K.talking_stats(Qf, Kf, Wl, bl, ws, B, H, N, dh)
-    _, _, c0 = K.attn_merge_rows(ws, bl, B, H, N, K.fused_plan(B, N)[0])
+    _, _, c0 = K.talking_row_constants(Qf, Kf, Wl, bl, B, H, N, dh)
     M = torch.zeros(B, N, N, device=dev)
     return timed(lambda: K.attn_pmean(Qf, Kf, Wl, c0, M, 1.0 / H, B, H, N, dh))
 
