@@ -540,6 +540,13 @@ int spe_adamw_flat(float* p, float* g, float* m, float* v, long n, const long* s
                    const float* partials, int npartials, float max_norm, int write_grad, float grad_scale,
                    spe_stream_t stream);
 
+/* ---- gradient accumulation beside the flat buckets (reference engine.py:161-165 together with main.py:170-172: ONE
+ * optimizer step over world x batch images; on fewer GPUs the missing ranks become micro-steps, spe_amd/dp.py accum_steps).
+ * dst[i] = a[i] + b[i]; b == NULL: the bit copy dst[i] = a[i] (-0.0 and NaN payloads survive).  dst may alias a or b.
+ * Every pointer 16-B aligned (-2 otherwise, nothing written); n <= 0: nothing launched.  No atomics, no cross-lane sums:
+ * bitwise deterministic. */
+int spe_accum_flat(float* dst, const float* a, const float* b, long n, spe_stream_t stream);
+
 /* ---- diagnostic (never launched by the product): keep nwg workgroups resident for `micros` microseconds, streaming copies
  * through buf (buf_floats floats, 16-B aligned; NULL: idle spinning) - the one-GPU proxy for the CU / HBM share of an RCCL ring
  * running beside the backward (reference main.py:172: DistributedDataParallel overlaps its all-reduce with the backward);

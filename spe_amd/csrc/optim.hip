@@ -34,6 +34,38 @@ extern "C" int spe_sqnorm_partials(const float* g, long n, float* partials, int 
     return 0;
 }
 
+// Gradient accumulation beside the buckets (spe_amd/dp.py, accum_steps > 1): dst = a + b, or the bit copy dst = a when b is
+// NULL (not a + 0: -0.0 survives).  dst may alias a or b - every lane reads its own elements before it writes them, hence no
+// __restrict__.  No atomics, no cross-lane sums: bitwise deterministic.
+template <bool ADD>
+__global__ __launch_bounds__(256) void accum_flat_kernel(float* dst, const float* a, const float* b, long n) {
+    const long n4 = n & ~3L;
+    for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n4; i += (long)gridDim.x * 1024) {
+        float4 v = *reinterpret_cast<const float4*>(a + i);
+        if (ADD) {
+            const float4 w = *reinterpret_cast<const float4*>(b + i);
+            v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
+        }
+        *reinterpret_cast<float4*>(dst + i) = v;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n - n4) {           // scalar tail: n % 4 elements
+        const long i = n4 + threadIdx.x;
+        const float x = a[i];
+        dst[i] = ADD ? x + b[i] : x;
+    }
+}
+
+// C-ABI: see include/spe_hip.h (spe_accum_flat).
+extern "C" int spe_accum_flat(float* dst, const float* a, const float* b, long n, hipStream_t st) {
+    if (n <= 0) return 0;
+    if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) return -2;
+    long nb = (n + 1023) / 1024; if (nb > 2048) nb = 2048;           // the grid cap of spe_adamw_flat
+    if (b != nullptr) hipLaunchKernelGGL(accum_flat_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, dst, a, b, n);
+    else hipLaunchKernelGGL(accum_flat_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, dst, a, b, n);
+    SPE_CHECK_LAUNCH();
+    return 0;
+}
+
 #define ADAMW_MAXSEG 64
 struct AdamwArgs {
     float* p; float* g; float* m; float* v; long n;

@@ -30,7 +30,7 @@ class _EventWork:
 
 class GradAllReducer:
     def __init__(self, params, bucket_bytes=64 << 20, average=True, group=None, flatten_params=False, broadcast=True,
-                 always_reduce=False, wire_dtype=None, buffers=(), comm=None, cu_reserve=None):
+                 always_reduce=False, wire_dtype=None, buffers=(), comm=None, cu_reserve=None, accum_steps=1):
         """flatten_params: also move the parameters themselves into flat per-bucket buffers with the gradient layout
         (param.data becomes a view) - what spe_amd.optim.FlatAdamW steps in one launch per bucket.  Construct the
         reducer AFTER the model is on its device: `module.to(...)` / `.cuda()` re-allocates parameters and would
@@ -47,7 +47,11 @@ class GradAllReducer:
         single-round attention grids shrink from 512 to 512 - cu_reserve workgroups).  Default for world > 1: the channel cap
         NCCL_MAX_NCHANNELS (bench.py sets 32 before the process group is created), else 32; 0 in a one-rank job.  Measured with
         tools/dp_proxy.py (a one-GPU proxy, not RCCL): foreign workgroups beside the step cost +9 % with the solo grids and
-        +3 % with 32 slots reserved (profiles/r03_dp_proxy.json)."""
+        +3 % with 32 slots reserved (profiles/r03_dp_proxy.json).
+        accum_steps: gradient accumulation - a cycle is accum_steps rounds of reset() / backward / finish() followed by ONE
+        optimizer step (the reference's effective batch of world x batch images, engine.py:161-165 + main.py:170-172, on fewer
+        GPUs).  The producers keep overwriting the buckets every backward; the running sum lives in one more buffer per bucket
+        (`acc`) and is merged into the bucket on the last micro-step, right before the bucket's collective.  See _launch()."""
         self.params = [p for p in params if p.requires_grad]
         self.flatten_params = flatten_params
         self.group = group
@@ -112,6 +116,9 @@ class GradAllReducer:
         self._fired = set()
         self._static_unused = None
         self._zero_views = None
+        self.accum_steps = 1
+        self.micro = 0              # 0-based index of the current backward within the cycle; finish() advances it
+        self.set_accum_steps(accum_steps)
         self.reset()
 
     def _make_bucket(self, plist):
@@ -137,7 +144,38 @@ class GradAllReducer:
         # wire_dtype: the send / receive buffer of the bucket in the wire format, allocated once (not per step)
         wire = torch.empty(n, device=dev, dtype=self.wire_dtype) if self.wire_dtype is not None else None
         self.buckets.append({"flat": flat, "flat_p": flat_p, "offsets": offsets, "params": list(plist), "pending": 0,
-                             "work": None, "wire": wire})
+                             "work": None, "wire": wire, "acc": None})
+
+    def set_accum_steps(self, k):
+        """Backward passes per optimizer step from the next cycle on.  Only at a cycle boundary: the running sums of an open
+        cycle belong to the old divisor."""
+        k = int(k)
+        if k < 1:
+            raise ValueError("GradAllReducer: accum_steps must be >= 1")
+        if self.micro != 0:
+            raise RuntimeError(f"GradAllReducer: accum_steps cannot change inside a cycle (micro-step {self.micro} of "
+                               f"{self.accum_steps}); finish the cycle or call restart_cycle()")
+        self.accum_steps = k
+        if k > 1:
+            for b in self.buckets:          # lazily: a reducer that never accumulates never pays for the buffers
+                if b["acc"] is None:
+                    b["acc"] = torch.empty_like(b["flat"])    # never zeroed: micro-step 0 overwrites it
+
+    def restart_cycle(self):
+        """Drop a half-finished cycle (recovery after an exception in a micro-step): the next backward is micro-step 0 again
+        and the running sums are overwritten by it."""
+        self.micro = 0
+        self.reset()
+
+    def _accum(self, dst, a, b=None):
+        """dst = a + b (b None: dst = a, a bit copy) on whole bucket-sized buffers; dst may be a or b."""
+        if dst.is_cuda:
+            from . import kernels as _K
+            _K.accum_flat(dst, a, b)
+        elif b is None:
+            dst.copy_(a)
+        else:
+            torch.add(a, b, out=dst)
 
     # Gradients of parameters with more than ZERO_MAX elements are always OVERWRITTEN by their producer (GEMM stores, split-K slab
     # sums with accumulate = 0, or the copy in _on_grad); only the small ones (biases, LayerNorm / LayerScale vectors, head mixers:
@@ -185,6 +223,14 @@ class GradAllReducer:
 
     def _launch(self, b):
         self._flush_deferred()                 # the bucket's deferred sums land before it is reduced / handed to the optimiser
+        if self.accum_steps > 1:
+            with torch.no_grad():
+                if self.micro < self.accum_steps - 1:
+                    # not the last micro-step: the bucket joins the running sum and stays on this rank (no collective, no wire copy)
+                    self._accum(b["acc"], b["flat"] if self.micro == 0 else b["acc"], None if self.micro == 0 else b["flat"])
+                    b["work"] = "local"
+                    return
+                self._accum(b["flat"], b["acc"], b["flat"])       # ((g_0 + g_1) + ...) + g_last, then exactly the path below
         if self.collective:
             buf = b["flat"]
             if self.wire_dtype is not None:
@@ -232,7 +278,9 @@ class GradAllReducer:
             self._next += 1
 
     def finish(self):
-        """Reduce buckets that never filled (unused parameters), wait for every collective, average."""
+        """Reduce buckets that never filled (unused parameters), wait for every collective, average.  With accum_steps > 1 only the
+        last finish() of a cycle waits and averages (by world * accum_steps); the others end after the buckets joined the
+        running sums, and p.grad holds that micro-step's own gradient."""
         self._flush_deferred()
         if self._static_unused is not None:
             # a LARGE parameter that fired in the first step but not in this one still holds the previous step's gradient (its
@@ -252,6 +300,10 @@ class GradAllReducer:
             _K.defer_reductions([b["flat"] for b in self.buckets])
             self._defer = _K._DEFER_FLATS is not None
             self._defer_wanted = False
+        if self.micro < self.accum_steps - 1:
+            self.micro += 1
+            return
+        self.micro = 0
         ev = None
         if self.measure and self.collective:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -267,17 +319,19 @@ class GradAllReducer:
         if ev is not None:          # compute-stream time between "backward enqueued" and "last collective done"
             ev[1].record()
             self._wait_events.append(ev)
-        if self.average and self.world > 1 and not self.average_in_optimizer:
-            torch._foreach_div_([b["flat"] for b in self.buckets], float(self.world))
+        if self.average and self.world * self.accum_steps > 1 and not self.average_in_optimizer:
+            torch._foreach_div_([b["flat"] for b in self.buckets], float(self.world * self.accum_steps))
 
     def averaged_grad(self, p):
         """The gradient of `p` as DDP would leave it in p.grad (the mean over ranks), whatever the averaging mode: with a
-        FlatAdamW attached the buckets hold the world SUM after finish() and the 1/world is applied inside its update launch."""
+        FlatAdamW attached the buckets hold the SUM over ranks and micro-steps after the cycle's last finish() and the
+        1/(world * accum_steps) is applied inside its update launch."""
         return self._views[p] * self.grad_scale()
 
     def grad_scale(self):
-        """Factor the optimizer still has to apply to the bucket contents (1/world when the averaging is folded in)."""
-        return 1.0 / self.world if (self.average and self.average_in_optimizer and self.world > 1) else 1.0
+        """Factor the optimizer still has to apply to the bucket contents (1/(world * accum_steps) when the averaging is folded in)."""
+        n = self.world * self.accum_steps
+        return 1.0 / n if (self.average and self.average_in_optimizer and n > 1) else 1.0
 
     def exposed_ms_mean(self):
         """Mean compute-stream stall of finish() in ms (call after a device synchronisation; needs measure = True)."""

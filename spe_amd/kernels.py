@@ -1592,6 +1592,18 @@ def adamw_flat(p, g, m, v, seg_end_i64, seg_lr, seg_wd, beta1, beta2, eps, bias_
           float(max_norm), int(bool(write_grad)), float(grad_scale), _st())
 
 
+def accum_flat(dst, a, b=None):
+    """dst = a + b on flat fp32 buffers of equal size (dst may be a or b); b None: dst = a, bit for bit."""
+    _chk(dst, a, b)
+    n = dst.numel()
+    if a.numel() != n or (b is not None and b.numel() != n):
+        raise ValueError("accum_flat: dst, a and b must have the same number of elements")
+    if not (dst.is_contiguous() and a.is_contiguous() and (b is None or b.is_contiguous())):
+        raise ValueError("accum_flat: contiguous buffers only")
+    _call("spe_accum_flat", _p(dst), _p(a), _p(b), n, _st())
+    return dst
+
+
 # ---- inference post-processing -----------------------------------------------------------------
 def nms_sorted(boxes, labels, iou_threshold, counts=None):
     """boxes [I,n,4] fp32 xyxy, labels [I,n] int64, per image ordered by (label asc, score desc) -> keep mask [I,n] bool."""

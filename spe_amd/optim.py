@@ -26,7 +26,8 @@ class FlatAdamW(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.reducer = reducer
         # Gradient averaging (1/world) rides on the update launch.  This changes what the reducer's buckets (and p.grad) hold
-        # after finish(): the world SUM, not DDP's mean - any other consumer must multiply by reducer.grad_scale() (or read
+        # after finish(): the SUM over ranks (and over the micro-steps of an accumulation cycle, 1/(world * accum_steps) then), not DDP's
+        # mean - any other consumer must multiply by reducer.grad_scale() (or read
         # reducer.averaged_grad(p)).  A reducer can therefore serve ONE FlatAdamW and nothing that expects means.
         if getattr(reducer, "_folded_into", None) not in (None, id(self)):
             raise ValueError("FlatAdamW: this GradAllReducer already folds its averaging into another optimizer")
@@ -76,6 +77,9 @@ class FlatAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if getattr(self.reducer, "micro", 0) != 0:
+            raise RuntimeError(f"FlatAdamW.step() inside an accumulation cycle: micro-step {self.reducer.micro} of accum_steps = "
+                               f"{self.reducer.accum_steps} comes next - run the remaining backward passes (or reducer.restart_cycle())")
         self._step += 1
         self._step_t += 1
         b1, b2 = self.param_groups[0]["betas"]
@@ -111,7 +115,8 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none=True):
         """The reference loop calls optimizer.zero_grad() before backward (engine.py:161): the gradients live in the
-        reducer's buckets, so this re-arms them (zeroes the buckets, detaches .grad, resets the bucket counters)."""
+        reducer's buckets, so this re-arms them (zeroes the buckets, detaches .grad, resets the bucket counters).  Inside an
+        accumulation cycle it is called before every backward all the same: the running sums live beside the buckets."""
         self.reducer.reset()
 
     def load_state_dict(self, state_dict):

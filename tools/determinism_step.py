@@ -1,7 +1,10 @@
 """Whole-step determinism: the training step of bench.py (forward, both criteria, backward, clip, AdamW) run twice from the same
 initial state must leave bitwise equal gradients after step 1 and bitwise equal parameters after step 2.
 
-    python tools/determinism_step.py [--depth 4] [--height 800 --width 1333] [--enc-layers 0] [--runs 3]
+    python tools/determinism_step.py [--depth 4] [--height 800 --width 1333] [--enc-layers 0] [--runs 3] [--accum 1]
+
+--accum K: every optimizer step is a gradient-accumulation cycle of K micro-batches (GradAllReducer(accum_steps=K)); the
+gradients compared are those after the first cycle's last backward (the sum over its micro-batches).
 
 Prints, per run beyond the first, the parameters whose gradient / value differs from run 0 (name, max abs difference); exit
 status 1 if any does.  tests/test_determinism_gpu.py runs the same function at a small size."""
@@ -14,8 +17,10 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 
-def run_steps(dev, depth=4, H=800, W=1333, batch=2, enc_layers=0, steps=2, precision="bf16s", noise=None, dropout=0.1):
-    """-> (names, gradients after the first backward, parameters after `steps` steps)"""
+def run_steps(dev, depth=4, H=800, W=1333, batch=2, enc_layers=0, steps=2, precision="bf16s", noise=None, dropout=0.1,
+              accum_steps=1):
+    """-> (names, gradients after the first backward (accum_steps > 1: after the first cycle), parameters after `steps` steps,
+    last loss)"""
     import bench
     from spe_amd import kernels as K
     from spe_amd.dp import GradAllReducer
@@ -45,25 +50,28 @@ def run_steps(dev, depth=4, H=800, W=1333, batch=2, enc_layers=0, steps=2, preci
     wd = crit.weight_dict
     named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
     params = [p for _, p in named]
-    reducer = GradAllReducer(params, flatten_params=True)
+    reducer = GradAllReducer(params, flatten_params=True, accum_steps=accum_steps)
     groups = [{"params": [p for n, p in named if "backbone" not in n], "lr": 1e-4},
               {"params": [p for n, p in named if "backbone" in n], "lr": 1e-5}]
     opt = FlatAdamW(groups, reducer, lr=1e-4, weight_decay=1e-4, max_grad_norm=0.1)
-    img, mask, targets = bench.synth_batch(4321, dev, batch=batch, H=H, W=W)
-    samples = NestedTensor(img, mask)
+    micro = []                                  # one batch per micro-step of a cycle: seeds 4321, 4322, ...
+    for k in range(accum_steps):
+        img, mask, targets = bench.synth_batch(4321 + k, dev, batch=batch, H=H, W=W)
+        micro.append((NestedTensor(img, mask), targets))
     grads = None
     for s in range(steps):
-        reducer.reset()
-        out = model(samples)
-        l0 = crit(out[0], targets)
-        with torch.no_grad():
-            ps = bench.pseudo_labels(rpp, out[0], targets)
-        l1 = crit_r(out[1], ps)
-        total = bench.weighted_total(l0, l1, wd)
-        if noise is not None:
-            noise()                             # foreign kernels between forward and backward: different scheduling run to run
-        total.backward()
-        reducer.finish()
+        for samples, targets in micro:
+            reducer.reset()
+            out = model(samples)
+            l0 = crit(out[0], targets)
+            with torch.no_grad():
+                ps = bench.pseudo_labels(rpp, out[0], targets)
+            l1 = crit_r(out[1], ps)
+            total = bench.weighted_total(l0, l1, wd)
+            if noise is not None:
+                noise()                         # foreign kernels between forward and backward: different scheduling run to run
+            total.backward()
+            reducer.finish()
         if s == 0:
             grads = [p.grad.detach().clone() if p.grad is not None else None for p in params]
         opt.step()
@@ -92,6 +100,7 @@ def main():
     ap.add_argument("--enc-layers", type=int, default=0)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--precision", default="bf16s")
+    ap.add_argument("--accum", type=int, default=1, help="micro-batches per optimizer step (gradient accumulation)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     xs = torch.randn(2048, 1024, device=dev)
@@ -99,7 +108,7 @@ def main():
     nbad = 0
     for r in range(a.runs):
         noise = None if r == 0 else (lambda r=r: [(xs @ xs.t()[:, :512]).sum() for _ in range(r)])
-        names, g, p, loss = run_steps(dev, a.depth, a.height, a.width, a.batch, a.enc_layers, 2, a.precision, noise)
+        names, g, p, loss = run_steps(dev, a.depth, a.height, a.width, a.batch, a.enc_layers, 2, a.precision, noise, accum_steps=a.accum)
         print(f"run {r}: loss {loss!r}")
         if ref is None:
             ref = (g, p)
