@@ -35,7 +35,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * the flash-style talking-heads entry points spe_talking_flash_* are new; 6 (round 5): spe_talking_bwdq_* are new; 7 (round 6): ONE attention
  * backward composition - spe_talking_fused(_bits / _plan), spe_attn_merge, spe_talking_flash_rows, spe_talking_flash_dv, spe_talking_bwdq_pass1 removed,
  * spe_talking_stats(_plan) new (the statistics pass alone), spe_rowdot new, spe_layernorm_res_bwd takes dy2.  Still 7 after purely additive
- * entry points: spe_conv_head_fwd / _plan / _bwd and spe_attn_pmean(_dense) (the woct0head backbones' conv class head and patch-affinity CAMs) */
+ * entry points: spe_conv_head_fwd / _plan / _bwd and spe_attn_pmean(_dense) (the woct0head backbones' conv class head and patch-affinity CAMs),
+ * spe_gemm_bf16nt_plan (the kernel selection of the 16-bit NT GEMM family, host only) - 82 entry points */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -204,6 +205,16 @@ int spe_gemm_bf16nt_exd(const void* A16, const void* B16, const void* A16lo, con
                         const float* res, const float* rgamma, int M, int N, int K, long lda, long ldb, long ldc, float alpha, int act,
                         int half_flags, float p_drop, uint64_t seed, uint64_t offset, const float* sample_scale, long rows_per_sample,
                         spe_stream_t stream);
+/* spe_gemm_bf16nt_plan: which kernel instance spe_gemm_bf16nt (ex = 0) / spe_gemm_bf16nt_ex(d) (ex = 1) run for a problem - the nn.Linear
+ * products of reference models/cait.py:376,390,409 and models/transformer.py:368-425, 389-396 (see above).  Host only: no device, no
+ * stream, nothing is launched; the launcher calls the same function (csrc/gemm_nt_select.h), so tests and tools can tell which kernel a
+ * shape exercises.  split: A16lo / B16lo given; f16_operands: act bit 8 / half_flags bit 2; f16_second: half_flags bit 3; splitk as passed
+ * to spe_gemm_bf16nt (1, or -n slabs); has_out16t / ld16t: the transposed copy of the extended epilogue.
+ * plan[9] = { family (0: gemm_nt2_kernel - LDS-DMA ring, >= 2048 rows; 1: gemm_bf16nt_kernel - register-pipelined), BM, BN, BK,
+ * NST (ring stages; family 1: 0), NTS (family 1: K tiles in flight at once, 0 = pipelined loop), SPLIT, EX, F16 }.
+ * Returns the negative status the GEMM entry would return when no kernel covers the problem (-2), else 0. */
+int spe_gemm_bf16nt_plan(int M, int N, int K, int split, int ex, int f16_operands, int f16_second, int splitk, int has_out16t,
+                         long ld16t, int* plan);
 int spe_cvt_bf16(const float* x, long ldx, int R, int C, void* out, void* out_lo, long ldo, void* outT, long ldt, float* colsum,
                  const float* aux, int act, spe_stream_t stream);
 /* spe_cvt_bf16_h (round 5): out = bf16(x), out_h = IEEE fp16(x) (saturating; same layout as out), outT as above - one pass. */

@@ -11,6 +11,7 @@
 // Block = 256 threads = 4 waves (2x2); block tile 128x128x32; wave tile 64x64 = 4x4 MFMA tiles.
 // Register-staged double buffering: tile t+1 is in flight from HBM while tile t is multiplied.
 #include "common.h"
+#include "gemm_tiles.h"
 #include <stdlib.h>
 
 #define BK 32
@@ -250,19 +251,9 @@ __global__ __launch_bounds__(256) void spe_gemm_kernel(GemmArgs p) {
     auto sA = [&](int buf, int pl) { return smem + (buf * 2 * NPL + pl) * TILE; };
     auto sB = [&](int buf, int pl) { return smem + (buf * 2 * NPL + NPL + pl) * TILE; };
 
-    // XCD-aware tile mapping: workgroup b runs on XCD b % 8 (8 private L2s).  The panels of the LARGER operand
-    // are bound to XCDs (all tiles that read one such panel run on the same XCD), so that operand is fetched
-    // into one L2 only; the smaller operand is re-fetched by each XCD.
     const int tiles_m = (p.M + T - 1) / T, tiles_n = (p.N + T - 1) / T;
     int tm, tn;
-    if (p.xcd_bind == 0) { tm = blockIdx.x % tiles_m; tn = blockIdx.x / tiles_m; }
-    else {
-        const int no = (p.xcd_bind == 1) ? tiles_n : tiles_m;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        const int tb = xcd + 8 * (idx / no), to = idx % no;
-        tm = (p.xcd_bind == 1) ? tb : to; tn = (p.xcd_bind == 1) ? to : tb;
-        if (tm >= tiles_m || tn >= tiles_n) return;
-    }
+    if (!tile_decode(p.xcd_bind, tiles_m, tiles_n, tm, tn)) return;      // XCD-aware tile order: gemm_tiles.h
     const int zb = blockIdx.z / p.splitk, zs = blockIdx.z % p.splitk;
     const int b0 = zb / p.nb1, b1 = zb % p.nb1;
     const float* A = p.a_bf16 ? nullptr : p.A + b0 * p.sA0 + b1 * p.sA1;
@@ -419,18 +410,10 @@ static int launch_gemm_t(const GemmArgs& p, int nbatch, hipStream_t stream) {
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    const int tiles_m = (p.M + T - 1) / T, tiles_n = (p.N + T - 1) / T;
+    const TileOrder order = tile_order(p.M, p.N, (p.M + T - 1) / T, (p.N + T - 1) / T);
     GemmArgs q = p;
-    // bind the operand with more bytes (same K: more rows) if it has enough panels to balance 8 XCDs
-    q.xcd_bind = 0;
-    if (p.M >= p.N && tiles_m >= 16) q.xcd_bind = 1;
-    else if (p.N > p.M && tiles_n >= 16) q.xcd_bind = 2;
-    else if (tiles_m >= 16) q.xcd_bind = 1;
-    else if (tiles_n >= 16) q.xcd_bind = 2;
-    int tiles = tiles_m * tiles_n;
-    if (q.xcd_bind == 1) tiles = 8 * ((tiles_m + 7) / 8) * tiles_n;
-    if (q.xcd_bind == 2) tiles = 8 * ((tiles_n + 7) / 8) * tiles_m;
-    dim3 grid(tiles, 1, nbatch * p.splitk);
+    q.xcd_bind = order.xcd_bind;
+    dim3 grid(order.grid, 1, nbatch * p.splitk);
     hipLaunchKernelGGL((spe_gemm_kernel<T, TA, TB, SPLIT>), grid, dim3(256), smem, stream, q);
     SPE_CHECK_LAUNCH();
     return 0;

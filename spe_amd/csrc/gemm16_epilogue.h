@@ -1,4 +1,4 @@
-// Epilogues of the bf16-operand NT GEMMs (gemm_bf16.hip: register-pipelined / ring kernels; gemm_nt2.hip: 128-wide LDS-DMA
+// Epilogues of the bf16-operand NT GEMMs (gemm_bf16.hip: register-pipelined kernels; gemm_nt2.hip: LDS-DMA ring
 // kernels), shared so that every kernel family writes bit-identical results for the same accumulators.
 // Ownership (MFMAs issued as (B-frag, A-frag)): acc[i][j][r] = C[m0 + wm*WM + i*16 + (lane&15)][n0 + wn*WN + j*16 + (lane>>4)*4 + r],
 // WM = BM/2, WN = BN/2, 4 waves as 2 x 2: a lane owns 4 consecutive columns of one row per 16x16 tile (16-B fp32 stores).
@@ -21,7 +21,7 @@ struct Gemm16Args {
     int act;                   // 0 none, 1 relu, 2 gelu(erf)
     int splitk; long slab; int kt_per_split;
     int xcd_bind;              // 0: plain tile order, 1: M-panels bound to XCDs, 2: N-panels bound to XCDs
-    int stagger;               // gemm_nt2.hip: start delay of the second-slot workgroups (units of ~4 us)
+    int stagger;               // gemm_nt2.hip: start delay of the second-slot workgroups (units of ~4 us); always 0
     // extended epilogue (spe_gemm_bf16nt_ex): bf16 copies of the result for the NEXT GEMMs, column sums, and the
     // derivative of a fused activation applied from its saved argument
     unsigned short* out16; long ld16;      // [M][ld16]  bf16(v)

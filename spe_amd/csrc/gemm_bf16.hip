@@ -22,10 +22,16 @@
 // Block = 256 threads = 4 waves (2x2); block tile BM x BN x 64 (BM, BN in {128, 64}); v_mfma_f32_16x16x32_bf16.
 // Pipeline per workgroup: tile t is multiplied out of LDS buffer t&1 while tile t+1 waits in registers and tile
 // t+2 is being fetched (16-B loads of 8 elements, no conversion work).
+//
+// This file holds the C-ABI entries of the whole 16-bit NT family and its one dispatch (nt_gemm_launch): gemm_nt_select.h maps a validated
+// problem to a kernel instance - the LDS-DMA ring kernels of gemm_nt2.hip for activation-sized products (>= 2048 rows), the kernels
+// below for everything else (fewer rows, K slabs, a transposed 16-bit copy, contractions that are no multiple of 64, N < 64).
 #include <cstdlib>
 #include "common.h"
 #include "gemm16_epilogue.h"
 #include "det_reduce.h"
+#include "gemm_nt_select.h"
+#include "gemm_tiles.h"
 
 // thread t fetches 16-B chunk (t & 7) of rows (t >> 3) + 32*i ; rows are clamped (never stored), chunks past K zeroed
 template <int R>
@@ -54,24 +60,10 @@ __device__ __forceinline__ void g16_stage(unsigned short* lds, const u32x4g_t (&
 // load round trips of the pipelined loop - 10 us for 0.1 GFLOP): all NTS K tiles of the workgroup are requested at once
 // (NTS * (BM + BN) / 32 16-B registers per thread), staged into NTS LDS slots behind ONE wait and barrier, then multiplied
 // back to back.  K tiles past the contraction length load zeros.
-// RING > 0 ("ring" variant, long contractions): the K tiles travel global -> LDS by global_load_lds_dwordx4 (no staging
-// registers, nothing for hipcc to drain at the loop head) into a ring of RING stages; RING - 1 tiles are in flight per
-// workgroup and a counted s_waitcnt vmcnt admits the oldest.  The pipelined loop below keeps ONE tile in flight beyond the one
-// waiting in registers, so an iteration lasts (memory latency) / 2 ~ 1 us when its MFMAs need 0.1 us (fc2 forward, K = 1536:
-// 24 iterations = 20 of its 29 us).  A DMA instruction deposits lane l's 16 B at (base + 16 l): 8 rows x 128 B per wave
-// instruction, rows unpadded - so the 16-B chunks of a row are XOR-swizzled by the row index through the choice of the GLOBAL
-// chunk each lane fetches (LDS slot (r, c) holds chunk c ^ (r & 7)), which leaves the operand reads 2-way conflicted at worst.
-// Needs K % 64 == 0 (every model dimension is).
-__device__ __forceinline__ void gb_glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-template <int BM, int BN, bool EX, int NTS = 0, int RING = 0, bool SPLIT = false>
+template <int BM, int BN, bool EX, int NTS, bool SPLIT>
 __global__ __launch_bounds__(256) void gemm_bf16nt_kernel(Gemm16Args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned short smem16[];
-    static_assert(!SPLIT || (NTS == 0 && RING == 0), "split operands run on the register-pipelined loop");
+    static_assert(!SPLIT || NTS == 0, "split operands run on the register-pipelined loop");
     constexpr int NFM = BM / 32, NFN = BN / 32;        // 16x16 MFMA tiles per wave (wave tile BM/2 x BN/2)
     constexpr int WM = BM / 2, WN = BN / 2;
     constexpr int TA_ = BM * GB_LDR, TB_ = BN * GB_LDR;
@@ -81,19 +73,9 @@ __global__ __launch_bounds__(256) void gemm_bf16nt_kernel(Gemm16Args p) {
     auto sAl = [&](int buf) { return smem16 + buf * BUF_ + TA_ + TB_; };
     auto sBl = [&](int buf) { return smem16 + buf * BUF_ + 2 * TA_ + TB_; };
 
-    // workgroup b runs on XCD b % 8: the panels of the operand with more rows are bound to XCDs (all tiles reading
-    // one such panel run on the same XCD), so that operand is fetched into one L2 only; the other one is re-fetched
-    // per XCD.  Same mapping as spe_gemm_kernel.
     const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
     int tm, tn;
-    if (p.xcd_bind == 0) { tm = blockIdx.x % tiles_m; tn = blockIdx.x / tiles_m; }
-    else {
-        const int no = (p.xcd_bind == 1) ? tiles_n : tiles_m;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        const int tb = xcd + 8 * (idx / no), to = idx % no;
-        tm = (p.xcd_bind == 1) ? tb : to; tn = (p.xcd_bind == 1) ? to : tb;
-        if (tm >= tiles_m || tn >= tiles_n) return;
-    }
+    if (!tile_decode(p.xcd_bind, tiles_m, tiles_n, tm, tn)) return;
     const int zs = blockIdx.z;
     float* C = p.C + (long)zs * p.slab;
     const int m0 = tm * BM, n0 = tn * BN;
@@ -112,57 +94,6 @@ __global__ __launch_bounds__(256) void gemm_bf16nt_kernel(Gemm16Args p) {
 #pragma unroll
         for (int j = 0; j < NFN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-    if constexpr (RING > 0) {
-        constexpr int STG = (BM + BN) * 64;               // bf16 per stage: rows of 64 elements = 128 B, unpadded
-        constexpr int PW = (BM + BN) / 32;                // 1-KB pieces (8 rows) per wave and stage
-        const int ws = __builtin_amdgcn_readfirstlane(w);
-        const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned short*)smem16);
-        auto issue = [&](int t, int slot) {
-            const int tc = min(t, nt - 1);                // past the range: a valid tile, never used (keeps the vmcnt arithmetic static)
-            const long k0 = (long)(kt_begin + tc) * GB_BK;
-#pragma unroll
-            for (int i = 0; i < PW; ++i) {
-                const int piece = ws + 4 * i;             // [0, BM/8): A rows ; [BM/8, (BM+BN)/8): B rows
-                const bool isA = piece < BM / 8;
-                const int r8 = (isA ? piece : piece - BM / 8) * 8 + (lane >> 3);
-                const int c = (lane & 7) ^ (r8 & 7);
-                const unsigned short* src = isA ? p.A + (long)min(m0 + r8, p.M - 1) * p.lda + k0 + c * 8
-                                                : p.B + (long)min(n0 + r8, p.N - 1) * p.ldb + k0 + c * 8;
-                gb_glds16(src, lds0 + (unsigned)((slot * STG + piece * 512) * 2));
-            }
-        };
-#pragma unroll
-        for (int st = 0; st < RING - 1; ++st) issue(st, st);
-        for (int t = 0; t < nt; ++t) {
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"((RING - 2) * PW) : "memory");     // this wave's pieces of tile t have landed
-            __syncthreads();                              // everybody's have, and everybody is done reading tile t - 1
-            issue(t + RING - 1, (t + RING - 1) % RING);   // refill the slot of tile t - 1
-            const unsigned short* tA = smem16 + (t % RING) * STG;
-            const unsigned short* tB = tA + BM * 64;
-#pragma unroll
-            for (int ks = 0; ks < GB_BK / 32; ++ks) {
-                const int kc = ks * 4 + (lane >> 4);
-                bf16x8_t a[NFM], b[NFN];
-#pragma unroll
-                for (int i = 0; i < NFM; ++i) {
-                    const int row = wm * WM + i * 16 + fr;
-                    a[i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u16x8_t*>(tA + row * 64 + ((kc ^ (row & 7)) * 8)));
-                }
-#pragma unroll
-                for (int j = 0; j < NFN; ++j) {
-                    const int row = wn * WN + j * 16 + fr;
-                    b[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u16x8_t*>(tB + row * 64 + ((kc ^ (row & 7)) * 8)));
-                }
-#pragma unroll
-                for (int i = 0; i < NFM; ++i)
-#pragma unroll
-                    for (int j = 0; j < NFN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the ring before the epilogue reuses the buffers
-        __syncthreads();
-    }
     if constexpr (NTS > 0) {
         u32x4g_t ra[NTS][BM / 32], rb[NTS][BN / 32];
 #pragma unroll
@@ -209,7 +140,7 @@ __global__ __launch_bounds__(256) void gemm_bf16nt_kernel(Gemm16Args p) {
     for (int i = 0; i < SA_; ++i) nal[i] = (u32x4g_t){0u, 0u, 0u, 0u};
 #pragma unroll
     for (int i = 0; i < SB_; ++i) nbl[i] = (u32x4g_t){0u, 0u, 0u, 0u};
-    if (NTS == 0 && RING == 0 && nt > 0) {
+    if (NTS == 0 && nt > 0) {
         g16_load<BM>(p.A, p.lda, m0, p.M, kt_begin * GB_BK, p.K, ca);
         g16_load<BN>(p.B, p.ldb, n0, p.N, kt_begin * GB_BK, p.K, cb);
         if constexpr (SPLIT) {
@@ -290,35 +221,59 @@ __global__ __launch_bounds__(256) void gemm_bf16nt_kernel(Gemm16Args p) {
     gemm16_epilogue_plain<BM, BN>(p, acc, C, m0, n0);
 }
 
-// gemm_nt2.hip: the 128-row LDS-DMA kernels for activation-sized problems; SPE_NT2_NA = not covered, run the kernels of this file
-#define SPE_NT2_NA (-100)
-int spe_nt2_dispatch(const Gemm16Args& p, bool ex, hipStream_t stream);
-
-template <int BM, int BN, bool EX = false, int NTS = 0, int RING = 0, bool SPLIT = false>
+template <int BM, int BN, bool EX, int NTS, bool SPLIT>
 static int launch_gemm16(const Gemm16Args& p, hipStream_t stream) {
-    constexpr int smem = RING > 0 ? RING * (BM + BN) * 64 * (int)sizeof(unsigned short)
-                                  : (NTS > 0 ? NTS : 2) * (SPLIT ? 2 : 1) * (BM + BN) * GB_LDR * (int)sizeof(unsigned short);
-    static_assert(RING == 0 || !EX || RING * 64 >= 2 * GB_LDR, "the staged epilogue tiles must fit the ring");
+    constexpr int smem = (NTS > 0 ? NTS : 2) * (SPLIT ? 2 : 1) * (BM + BN) * GB_LDR * (int)sizeof(unsigned short);
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16nt_kernel<BM, BN, EX, NTS, RING, SPLIT>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16nt_kernel<BM, BN, EX, NTS, SPLIT>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, smem);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    const TileOrder order = tile_order(p.M, p.N, (p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
     Gemm16Args q = p;
-    q.xcd_bind = 0;
-    if (p.M >= p.N && tiles_m >= 16) q.xcd_bind = 1;
-    else if (p.N > p.M && tiles_n >= 16) q.xcd_bind = 2;
-    else if (tiles_m >= 16) q.xcd_bind = 1;
-    else if (tiles_n >= 16) q.xcd_bind = 2;
-    int tiles = tiles_m * tiles_n;
-    if (q.xcd_bind == 1) tiles = 8 * ((tiles_m + 7) / 8) * tiles_n;
-    if (q.xcd_bind == 2) tiles = 8 * ((tiles_n + 7) / 8) * tiles_m;
-    dim3 grid(tiles, 1, p.splitk);
-    hipLaunchKernelGGL((gemm_bf16nt_kernel<BM, BN, EX, NTS, RING, SPLIT>), grid, dim3(256), smem, stream, q);
+    q.xcd_bind = order.xcd_bind;
+    dim3 grid(order.grid, 1, p.splitk);
+    hipLaunchKernelGGL((gemm_bf16nt_kernel<BM, BN, EX, NTS, SPLIT>), grid, dim3(256), smem, stream, q);
     SPE_CHECK_LAUNCH();
+    return 0;
+}
+
+// gemm_nt2.hip: the LDS-DMA kernels for activation-sized problems, one explicit instantiation per entry of NT2_INSTANCES
+template <int BM, int BN, int BK, int NST, bool SPLIT, bool EX, bool F16>
+int launch_nt2(const Gemm16Args& p, hipStream_t stream);
+
+static NtProblem nt_problem(const Gemm16Args& p, bool ex) {
+    return NtProblem{p.M, p.N, p.K, p.Alo != nullptr, ex, (p.h16 & 1) != 0, (p.h16 & 4) != 0, p.splitk, p.out16T != nullptr, p.ld16t};
+}
+
+// The one dispatch of the family: the selection (gemm_nt_select.h) names an instance, the switch below holds every instance there is.
+static int nt_gemm_launch(const Gemm16Args& p, bool ex, hipStream_t stream) {
+    const NtPlan s = nt_gemm_select(nt_problem(p, ex));
+    if (s.err) return s.err;
+    switch (nt_key(s)) {
+#define NT2_CASE(BM, BN, BK, NST, SPLIT, EX, F16) \
+    case nt_key(NT_FAMILY_NT2, BM, BN, BK, NST, 0, SPLIT, EX, F16): return launch_nt2<BM, BN, BK, NST, SPLIT, EX, F16>(p, stream);
+#define BF16NT_CASE(BM, BN, EX, NTS, SPLIT) \
+    case nt_key(NT_FAMILY_BF16NT, BM, BN, 64, 0, NTS, SPLIT, EX, false): return launch_gemm16<BM, BN, EX, NTS, SPLIT>(p, stream);
+        NT2_INSTANCES(NT2_CASE)
+        BF16NT_INSTANCES(BF16NT_CASE)
+#undef NT2_CASE
+#undef BF16NT_CASE
+    }
+    return -2;          // unreachable while nt_gemm_select returns members of the two lists (tests/test_nt_gemm_plan_cpu.py)
+}
+
+// C-ABI: see include/spe_hip.h (spe_gemm_bf16nt_plan).  Host only: the selection for a problem, no device needed.
+extern "C" int spe_gemm_bf16nt_plan(int M, int N, int K, int split, int ex, int f16_operands, int f16_second, int splitk, int has_out16t,
+                                    long ld16t, int* plan) {
+    if (M <= 0 || N <= 0 || K <= 0 || splitk > 1 || !plan) return -2;
+    const NtPlan s = nt_gemm_select(NtProblem{M, N, K, split != 0, ex != 0, f16_operands != 0, f16_second != 0, splitk < 0 ? -splitk : 1,
+                                              has_out16t != 0, ld16t});
+    if (s.err) return s.err;
+    const int v[9] = {s.family, s.BM, s.BN, s.BK, s.NST, s.NTS, s.SPLIT, s.EX, s.F16};
+    for (int i = 0; i < 9; ++i) plan[i] = v[i];
     return 0;
 }
 
@@ -336,8 +291,8 @@ extern "C" int spe_gemm_bf16nt(const void* A16, const void* B16, const void* A16
     p.A = reinterpret_cast<const unsigned short*>(A16); p.B = reinterpret_cast<const unsigned short*>(B16);
     p.Alo = reinterpret_cast<const unsigned short*>(A16lo); p.Blo = reinterpret_cast<const unsigned short*>(B16lo); p.out16lo = nullptr;
     p.C = C; p.C2 = C2; p.bias = bias; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    // act bits 8, 9: IEEE fp16 operands (single-term, v_mfma_f32_16x16x32_f16) / IEEE fp16 output C [M][ldc] - the 128-wide LDS-DMA
-    // kernels only (gemm_nt2.hip); -2 when the problem is outside their domain
+    // act bits 8, 9: IEEE fp16 operands (single-term, v_mfma_f32_16x16x32_f16) / IEEE fp16 output C [M][ldc] - the LDS-DMA kernels
+    // only (gemm_nt2.hip); -2 when the problem is outside their domain
     p.h16 = (act >> 8) & 3; act &= 0xff;
     p.alpha = alpha; p.act = act; p.slab = 0;
     p.ws = DetWs{nullptr, nullptr, 0, 0}; p.half_flags = 0;
@@ -355,47 +310,7 @@ extern "C" int spe_gemm_bf16nt(const void* A16, const void* B16, const void* A16
     p.splitk = splitk;
     if (splitk > 1 && (act != 0 || C2 != nullptr || bias != nullptr)) return -3;
     if (p.Alo && splitk != 1) return -3;
-    { const int rc = spe_nt2_dispatch(p, false, stream); if (rc != SPE_NT2_NA) return rc; }
-    if (p.h16 & 1) return -2;
-    if (p.Alo) {            // split operands: 64x64 tiles at two workgroups per CU (73 KB of LDS each); 128x64 when that fills the chip less
-        if (splitk != 1) return -3;
-        return launch_gemm16<64, 64, false, 0, 0, true>(p, stream);
-    }
-    {   // developer knob (tools/bench_gemm.py): SPE_GEMM16_TILE = 1 / 2 / 3 forces 128x128 / 128x64 / 64x64
-        static const int forced = SPE_KNOB("SPE_GEMM16_TILE", 0);
-        if (forced == 1) return launch_gemm16<128, 128>(p, stream);
-        if (forced == 2) return launch_gemm16<128, 64>(p, stream);
-        if (forced == 3) return launch_gemm16<64, 64>(p, stream);
-    }
-    // Activation-sized products (many rows, one pass over a short or medium contraction): 64x64 tiles.  Measured inside the
-    // training step they beat the wider tiles by 10-30 % (qkv forward 39 -> 27 us, fc1 + GELU 70 -> 51 us): a workgroup's
-    // epilogue (bias / activation / up to three output tensors) is as long as its main loop here, 2000-3000 small
-    // workgroups at 4 per CU overlap one's stores with another's loads, and the 1.1-1.5 rounds that 585 / 780 wide tiles
-    // make on 512 slots disappear.  The weight-gradient products (few output tiles, split-K) keep the wide tiles.
-    if (splitk == 1 && M >= 2048) {
-        // long contraction into a narrow output (fc2 forward, fc1 / qkv input gradients, the stacked decoder projections'
-        // input gradient): 128x64 tiles fed by the LDS-DMA ring - half the A-panel re-reads of the 64x64 tiles and 2 tiles
-        // in flight per workgroup (K = 1536: 30.5 -> 25.6 us, K = 1152: 23.3 -> 20.7, K = 4608: 85 -> 64; with more stages
-        // or on the K = 384 products the lost occupancy costs more than the ring brings).  SPE_GEMM16_RING=0 disables it (A/B).
-        static const int ring = SPE_KNOB("SPE_GEMM16_RING", 1);
-        if (ring > 1 && (K % GB_BK) == 0) {          // developer knob: force a ring configuration for every activation-sized product
-            if (ring == 1282) return launch_gemm16<128, 128, false, 0, 2>(p, stream);
-            if (ring == 1283) return launch_gemm16<128, 128, false, 0, 3>(p, stream);
-            if (ring == 642) return launch_gemm16<128, 64, false, 0, 2>(p, stream);
-            if (ring == 643) return launch_gemm16<128, 64, false, 0, 3>(p, stream);
-        }
-        if (ring && (K % GB_BK) == 0 && K >= 1024 && N <= 512) return launch_gemm16<128, 64, false, 0, 3>(p, stream);
-        return launch_gemm16<64, 64>(p, stream);
-    }
-    // tile: 128x128 when that already fills the chip, else narrower tiles (more workgroups in flight)
-    const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128) * splitk;
-    if (t128 >= 384 && N > 64) return launch_gemm16<128, 128>(p, stream);
-    const long t64n = (long)((M + 127) / 128) * ((N + 63) / 64) * splitk;
-    if (t64n >= 256 && M > 64) return launch_gemm16<128, 64>(p, stream);
-    // decoder-size problems (few workgroups, short contraction): every K tile in flight at once
-    if (splitk == 1 && ktiles <= 6) return launch_gemm16<64, 64, false, 6>(p, stream);
-    if (splitk == 1 && ktiles == 7) return launch_gemm16<64, 64, false, 7>(p, stream);
-    return launch_gemm16<64, 64>(p, stream);
+    return nt_gemm_launch(p, false, stream);
 }
 
 // C-ABI: see include/spe_hip.h (spe_gemm_bf16nt_ex).  -2: unsupported alignment / leading dimensions.
@@ -452,29 +367,7 @@ static int gemm_bf16nt_ex_impl(const void* A16, const void* B16, const void* A16
     p.h16 = (op_f16 ? 1 : 0) | (lo_f16 ? 4 : 0);
     p.ws = spe_detws();
     if (colsum) DET_CHECK(p.ws, (N + 63) / 64, (M + 63) / 64, 64);      // bound for the smallest tiles
-    // the transposed copy's zero columns M..ld16t-1 are written by the last row tile: it must reach ld16t
-    const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-    const bool reach128 = !out16T || ld16t <= (long)((M + 127) / 128) * 128;
-    const bool reach64 = !out16T || ld16t <= (long)((M + 63) / 64) * 64;
-    if (!reach128 && !reach64) return -2;
-    { const int rc = spe_nt2_dispatch(p, true, stream); if (rc != SPE_NT2_NA) return rc; }
-    if (p.h16) return -2;                    // fp16 operands / fp16 second copy: the LDS-DMA kernels only
-    if (p.Alo) return reach64 ? launch_gemm16<64, 64, true, 0, 0, true>(p, stream) : -2;
-    {   // developer knob: SPE_GEMM16_TILE also applies here
-        static const int forced = SPE_KNOB("SPE_GEMM16_TILE", 0);
-        if (forced == 1 && reach128) return launch_gemm16<128, 128, true>(p, stream);
-        if (forced == 2 && reach128) return launch_gemm16<128, 64, true>(p, stream);
-        if (forced == 3 && reach64) return launch_gemm16<64, 64, true>(p, stream);
-    }
-    {   // see spe_gemm_bf16nt
-        static const int ring = SPE_KNOB("SPE_GEMM16_RING", 1);
-        if (ring && M >= 2048 && reach128 && (K % GB_BK) == 0 && K >= 1024 && N <= 512) return launch_gemm16<128, 64, true, 0, 3>(p, stream);
-    }
-    if (M >= 2048 && reach64) return launch_gemm16<64, 64, true>(p, stream);
-    if (reach128 && t128 >= 384 && N > 64) return launch_gemm16<128, 128, true>(p, stream);
-    const long t64n = (long)((M + 127) / 128) * ((N + 63) / 64);
-    if (reach128 && ((t64n >= 256 && M > 64) || !reach64)) return launch_gemm16<128, 64, true>(p, stream);
-    return launch_gemm16<64, 64, true>(p, stream);
+    return nt_gemm_launch(p, true, stream);
 }
 
 // ---- fp32 -> bf16 (round to nearest even) copies of a [R, C] matrix: out[R][ldo] (row-major) and/or the

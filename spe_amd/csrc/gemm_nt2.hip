@@ -24,12 +24,8 @@
 #include <cstdlib>
 #include "common.h"
 #include "gemm16_epilogue.h"
-
-__device__ __forceinline__ void nt2_glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
+#include "gemm_nt_select.h"
+#include "gemm_tiles.h"
 
 // chunk permutation of row `r`: an involution on the 16-B chunk index, applied to the global source and to the fragment reads
 template <int CPR>
@@ -39,7 +35,7 @@ __device__ __forceinline__ int nt2_swz(int r) {
 }
 
 // F16: the operands hold IEEE fp16 (single-term product on v_mfma_f32_16x16x32_f16: same bytes and rate as bf16, 3 more mantissa bits)
-template <int BM, int BN, int BK, int NST, bool SPLIT, bool EX, bool F16 = false>
+template <int BM, int BN, int BK, int NST, bool SPLIT, bool EX, bool F16>
 __global__ __launch_bounds__(256, 2) void gemm_nt2_kernel(Gemm16Args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned short smem16[];
     constexpr int NFM = BM / 32, NFN = BN / 32, WM = BM / 2, WN = BN / 2;
@@ -52,19 +48,14 @@ __global__ __launch_bounds__(256, 2) void gemm_nt2_kernel(Gemm16Args p) {
 
     const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
     int tm, tn;
-    if (p.xcd_bind == 0) { tm = blockIdx.x % tiles_m; tn = blockIdx.x / tiles_m; }
-    else {      // the panels of the operand with more rows are bound to XCDs (workgroup b runs on XCD b % 8): see gemm_bf16.hip
-        const int no = (p.xcd_bind == 1) ? tiles_n : tiles_m;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        const int tb = xcd + 8 * (idx / no), to = idx % no;
-        tm = (p.xcd_bind == 1) ? tb : to; tn = (p.xcd_bind == 1) ? to : tb;
-        if (tm >= tiles_m || tn >= tiles_n) return;
-    }
+    if (!tile_decode(p.xcd_bind, tiles_m, tiles_n, tm, tn)) return;
     const int m0 = tm * BM, n0 = tn * BN;
     // Phase stagger: the two workgroups of a CU start together and would run their main loops (operand loads + MFMA) and then their
     // epilogues (tens of MB of stores) in lockstep - neither overlaps the other's.  The workgroups that fill the second slot
     // of the CUs (grid indices 256-511 of the first round) start `stagger` x ~4 us late, so one's epilogue meets the other's loop;
     // later rounds inherit the offset.
+    // Measured: does not help (profiles/r03_gemm_ablation.txt), so the launcher always passes 0.  The dead branch stays for now: taking it and
+    // the field out of the kernel arguments moved the main loops and cost 5-9 % on three instances (profiles/nt_gemm_one_dispatch.txt).
     if (p.stagger > 0 && (blockIdx.x >> 8) == 1) {
         for (int i = 0; i < p.stagger; ++i) __builtin_amdgcn_s_sleep(127);
     }
@@ -103,7 +94,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt2_kernel(Gemm16Args p) {
             const unsigned short* base = isA ? (lo ? p.Alo : p.A) : (lo ? p.Blo : p.B);
             const unsigned short* src = isA ? base + (long)min(m0 + r, p.M - 1) * p.lda + k0 + gc * 8
                                             : base + (long)min(n0 + r, p.N - 1) * p.ldb + k0 + gc * 8;
-            nt2_glds16(src, lds0 + (unsigned)((slot * STE + piece * 512) * 2));
+            glds16(src, lds0 + (unsigned)((slot * STE + piece * 512) * 2));
         }
     };
 #pragma unroll
@@ -170,8 +161,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt2_kernel(Gemm16Args p) {
     else gemm16_epilogue_plain<BM, BN>(p, acc, p.C, m0, n0);
 }
 
-template <int BM, int BN, int BK, int NST, bool SPLIT, bool EX, bool F16 = false>
-static int launch_nt2(const Gemm16Args& p, hipStream_t stream) {
+// Launcher of one instance: called by the switch of gemm_bf16.hip (nt_gemm_launch) with validated arguments.  The instances that exist
+// are the explicit instantiations below - NT2_INSTANCES of gemm_nt_select.h, what nt_gemm_select can return for this family.
+template <int BM, int BN, int BK, int NST, bool SPLIT, bool EX, bool F16>
+int launch_nt2(const Gemm16Args& p, hipStream_t stream) {
     constexpr int ring = NST * ((BM + BN) / (64 / (BK / 8))) * (SPLIT ? 2 : 1) * 1024;
     constexpr int epi = EX ? BM * (BN + 8) * 2 * ((SPLIT || F16) ? 2 : 1) : 0;
     constexpr int smem = ring > epi ? ring : epi;
@@ -183,100 +176,19 @@ static int launch_nt2(const Gemm16Args& p, hipStream_t stream) {
         attr_set = true;
     }
     const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    const TileOrder order = tile_order(p.M, p.N, tiles_m, tiles_n);
     Gemm16Args q = p;
-    static const int stagger = SPE_KNOB("SPE_NT2_STAGGER", 0);
-    q.stagger = stagger;
-    q.xcd_bind = 0;
-    if (p.M >= p.N && tiles_m >= 16) q.xcd_bind = 1;
-    else if (p.N > p.M && tiles_n >= 16) q.xcd_bind = 2;
-    else if (tiles_m >= 16) q.xcd_bind = 1;
-    else if (tiles_n >= 16) q.xcd_bind = 2;
-    int tiles = tiles_m * tiles_n;
-    if (q.xcd_bind == 1) tiles = 8 * ((tiles_m + 7) / 8) * tiles_n;
-    if (q.xcd_bind == 2) tiles = 8 * ((tiles_n + 7) / 8) * tiles_m;
+    q.xcd_bind = order.xcd_bind;
+    q.stagger = 0;
     // column sums of the extended epilogue (a bias gradient): deferred when the caller said so - sets = column tiles, members = row tiles
     const DetDeferSeg sg[1] = {{q.colsum, q.N}};
     float* region = (EX && q.colsum) ? det_defer_try(tiles_n, tiles_m, BN, 1, sg, stream) : nullptr;
     if (region) q.ws.defer = region;
-    hipLaunchKernelGGL((gemm_nt2_kernel<BM, BN, BK, NST, SPLIT, EX, F16>), dim3(tiles), dim3(256), smem, stream, q);
+    hipLaunchKernelGGL((gemm_nt2_kernel<BM, BN, BK, NST, SPLIT, EX, F16>), dim3(order.grid), dim3(256), smem, stream, q);
     if (region) det_defer_commit(region, tiles_n, tiles_m, BN, 1, sg, 1);
     SPE_CHECK_LAUNCH();
     return 0;
 }
-
-// Called by spe_gemm_bf16nt / spe_gemm_bf16nt_ex (gemm_bf16.hip) with validated arguments.  Returns SPE_NT2_NA when this kernel
-// family does not cover the problem (the caller then runs its own kernels): fewer than 2048 rows, a contraction that is not a
-// multiple of the stage depth, a K split, or a transposed bf16 copy of the result.
-#define SPE_NT2_NA (-100)
-int spe_nt2_dispatch(const Gemm16Args& p, bool ex, hipStream_t stream) {
-    static const int enabled = SPE_KNOB("SPE_GEMM_NT2", 1);      // developer knob (A/B against gemm_bf16.hip)
-    const bool split = p.Alo != nullptr;
-    // fp16 operands have no other kernel family, so their domain reaches down to ONE stage (K = 64: issue() clamps the refill to the
-    // last tile); the bf16 products of a contraction that short are faster on gemm_bf16.hip's kernels
-    const int kmin = (p.h16 & 1) ? 64 : 128;
-    if (!enabled || p.M < 2048 || p.splitk != 1 || p.out16T || (p.K % 64) != 0 || p.K < kmin || p.N < 64) return SPE_NT2_NA;
-    if (!(p.h16 & 1) && (p.h16 & 4)) return -2;        // the fp16 second copy comes with fp16 operands only
-    if ((p.h16 & 1) && ex) {
-        // fp16 single-term operands with the extended epilogue (round 5: the backbone MLP's forward products in precision mode bf16s -
-        // fc1 + GELU emitting the bf16 copy for the backward and the fp16 copy for fc2, fc2 + LayerScale residual)
-        if (split) return -2;
-        if (p.N >= 1024) return launch_nt2<128, 128, 64, 2, false, true, true>(p, stream);
-        return launch_nt2<128, 64, 64, 2, false, true, true>(p, stream);
-    }
-    if (p.h16 & 1) {        // fp16 single-term operands (the decoder's memory-side projections): wide tiles, plain epilogue
-        if (split) return -2;
-        const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128), t160 = (long)((p.M + 159) / 160) * ((p.N + 127) / 128);
-        if (((t160 + 511) / 512) * 160 < ((t128 + 511) / 512) * 128) return launch_nt2<160, 128, 64, 2, false, false, true>(p, stream);
-        return launch_nt2<128, 128, 64, 2, false, false, true>(p, stream);
-    }
-    static const int wide_min = SPE_KNOB("SPE_NT2_WIDE_MIN", 1024);     // developer knob
-    // single-term products with the extended epilogue (fc2 dh: GELU derivative from the saved pre-activation, bf16 output, column
-    // sums) are bound by that epilogue: 128 x 64 tiles at three workgroups per CU overlap it with other workgroups' main loops
-    // (8300 x 1536 x 384: 63 -> 51 us); the split forward products and the plain-epilogue ones are faster on the wide tiles
-    static const int wide_min_ex1 = SPE_KNOB("SPE_NT2_WIDE_MIN_EX1", 2048);      // developer knob
-    // ... and so are the split forward products with the extended epilogue (fc1 + GELU: fp16 pre-activation + hi / lo bf16 outputs):
-    // 85 -> 73 us INSIDE the step on 128 x 64 tiles (the isolated launch prefers the wide tiles, 69 vs 76 us: measured in the step)
-    static const int wide_min_ex3 = SPE_KNOB("SPE_NT2_WIDE_MIN_EX3", 2048);           // developer knob
-    const bool wide = p.N >= (ex ? (split ? wide_min_ex3 : wide_min_ex1) : wide_min);
-    static const int cfg = SPE_KNOB("SPE_NT2_CFG", 0);      // developer knob: ring depth / stage depth variants
-#define NT2_GO(BK_, NST_, SP_)                                                                                                   \
-    do {                                                                                                                         \
-        if (ex) return wide ? launch_nt2<128, 128, BK_, NST_, SP_, true>(p, stream) : launch_nt2<128, 64, BK_, NST_, SP_, true>(p, stream);   \
-        return wide ? launch_nt2<128, 128, BK_, NST_, SP_, false>(p, stream) : launch_nt2<128, 64, BK_, NST_, SP_, false>(p, stream);         \
-    } while (0)
-    // Tile quantisation: 8300 rows make 65 row tiles of 128; 65 x 9 = 585 tiles (qkv forward) take 2 rounds on the 512 resident workgroup
-    // slots for 1.14 rounds of work.  160-row tiles (52 x 9 = 468) fit one round of 1.25x larger tiles.  Plain epilogue only (the staged
-    // epilogue of a 160 x 128 tile does not fit two workgroups per CU).
-    static const int tall = SPE_KNOB("SPE_NT2_TALL", 1);      // developer knob (A/B)
-    if (tall && !ex && wide && cfg == 0) {
-        const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128), t160 = (long)((p.M + 159) / 160) * ((p.N + 127) / 128);
-        const long c128 = ((t128 + 511) / 512) * 128, c160 = ((t160 + 511) / 512) * 160;
-        if (c160 < c128) return split ? launch_nt2<160, 128, 32, 2, true, false>(p, stream) : launch_nt2<160, 128, 64, 2, false, false>(p, stream);
-    }
-    // (A balanced single round for narrow outputs - 52 evenly spread 160-row panels x 4 column tiles of 96, one workgroup per CU, 3-stage ring - was
-    // measured slower in round 4 and is gone: profiles/r04_bench_nt.txt, profiles/HISTORY_r05.md.)
-    // Narrow outputs (N = 384: the input-gradient products, proj / fc2 forward): 8300 x 384 is 390 tiles of 128 x 64 - 1.5 workgroups
-    // per CU.  64 x 64 tiles (780 workgroups, three to four per CU) hide each other's load latency: qkv dx 19.4 -> 17.0 us, fc1 dx
-    // 24.0 -> 21.5, the stacked decoder dx (K = 4608) 59.3 -> 53.1.  SPE_NT2_SHORT: bit 0 single-term plain, bit 1 split plain,
-    // bit 2 split extended epilogue, bit 3 single-term extended epilogue (developer knob, A/B).
-    static const int short_rows = SPE_KNOB("SPE_NT2_SHORT", 9);      // in the step: fc2 dh 64.5 -> 56.3 us with bit 3; bits 1, 2 no gain
-    if (!wide && cfg == 0) {
-        if ((short_rows & 1) && !ex && !split) return launch_nt2<64, 64, 64, 2, false, false>(p, stream);
-        if ((short_rows & 2) && !ex && split) return launch_nt2<64, 64, 32, 2, true, false>(p, stream);
-        if ((short_rows & 4) && ex && split) return launch_nt2<64, 64, 32, 2, true, true>(p, stream);
-        if ((short_rows & 8) && ex && !split) return launch_nt2<64, 64, 64, 2, false, true>(p, stream);
-    }
-    if (split) {
-        if (cfg == 1) NT2_GO(32, 3, true);
-        if (cfg == 2) NT2_GO(32, 4, true);
-        NT2_GO(32, 2, true);
-    }
-    if (cfg == 1) NT2_GO(64, 3, false);
-    if (cfg == 2) NT2_GO(64, 4, false);
-    if (cfg == 3) NT2_GO(32, 4, false);
-    if (cfg == 4) NT2_GO(32, 6, false);
-    if (cfg == 5) NT2_GO(32, 2, false);
-    if (cfg == 6) NT2_GO(32, 3, false);
-    NT2_GO(64, 2, false);
-#undef NT2_GO
-}
+#define NT2_INSTANTIATE(BM, BN, BK, NST, SPLIT, EX, F16) template int launch_nt2<BM, BN, BK, NST, SPLIT, EX, F16>(const Gemm16Args&, hipStream_t);
+NT2_INSTANCES(NT2_INSTANTIATE)
+#undef NT2_INSTANTIATE

@@ -684,9 +684,22 @@ MLP_PRE_F16 = False      # module attribute (tests/test_kernels_gpu.py runs both
 MLP_F16 = True
 
 
+def gemm16_plan(M, N, K, split=False, ex=False, op_f16=False, lo_f16=False, splitk=1, out16T=False, ld16t=0):
+    """Which kernel instance gemm16 (ex=False) / gemm16_ex (ex=True) run for a problem (spe_gemm_bf16nt_plan, csrc/gemm_nt_select.h): a dict
+    with family "nt2" (gemm_nt2_kernel<BM,BN,BK,NST,SPLIT,EX,F16>) or "bf16nt" (gemm_bf16nt_kernel<BM,BN,EX,NTS,SPLIT>), or None
+    when no kernel covers it (the GEMM entry would fail).  Needs no device.  For tests and tools: no hot path calls it."""
+    v = (ctypes.c_int * 9)()
+    rc = lib.load().spe_gemm_bf16nt_plan(M, N, K, int(split), int(ex), int(op_f16), int(lo_f16), int(splitk), int(out16T), int(ld16t), v)
+    if rc != 0:
+        return None
+    return dict(family=("nt2", "bf16nt")[v[0]], BM=v[1], BN=v[2], BK=v[3], NST=v[4], NTS=v[5], SPLIT=bool(v[6]), EX=bool(v[7]), F16=bool(v[8]))
+
+
 def mlp_f16_ok(R, K, Hd, N):
-    # mirrors spe_nt2_dispatch (csrc/gemm_nt2.hip): the fp16-operand extended epilogue exists only there - M >= 2048, contraction % 64 == 0 and
-    # >= 128, >= 64 output columns, for BOTH products (fc1: K -> Hd, fc2: Hd -> N); anything else takes the split-bf16 path
+    # the fp16-operand extended epilogue exists only on the nt2 kernels (csrc/gemm_nt_select.h, "nt2 domain"): M >= 2048, contraction % 64 == 0,
+    # >= 64 output columns, for BOTH products (fc1: K -> Hd, fc2: Hd -> N); anything else takes the split-bf16 path.  Stricter than the table
+    # on purpose (the table takes fp16 operands from K = 64, this path starts at 128).  A Python predicate, not a library call: it runs per
+    # forward.  tests/test_nt_gemm_plan_cpu.py holds it to the table: True here implies an nt2 fp16 EX kernel for both products.
     return (MLP_F16 and split_fwd() and R >= 2048 and K % 64 == 0 and K >= 128 and Hd % 64 == 0 and Hd >= 128 and N % 8 == 0 and N >= 64)
 
 

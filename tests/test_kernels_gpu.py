@@ -1153,6 +1153,95 @@ def test_gemm_nt2_fused_epilogues(dev, M, N, Kd):
     assert rel(o16.float(), v) < 4e-3 and rel(cs, v.sum(0)) < 1e-4
 
 
+def _nt_case_id(p):
+    return "x".join(str(p[k]) for k in "MNK") + "".join("-" + k for k in ("split", "ex", "op_f16", "out16T") if p.get(k))
+
+
+def _gelu_prime(a64):
+    return 0.5 * (1 + torch.erf(a64 / 2 ** 0.5)) + a64 * torch.exp(-0.5 * a64 * a64) / (2 * 3.141592653589793) ** 0.5
+
+
+def _nt_cases():
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import nt_gemm_cases
+    return nt_gemm_cases
+
+
+@pytest.mark.parametrize("case", _nt_cases().GPU_CASES, ids=_nt_case_id)
+def test_nt_gemm_every_instance(dev, case):
+    """Every compiled instance of gemm_nt2_kernel (14) and gemm_bf16nt_kernel (10) at the smallest shape that selects it
+    (tests/nt_gemm_cases.py; tests/test_nt_gemm_plan_cpu.py proves the coverage), against fp64 on the operands the kernel sees.  Bounds, as
+    in test_gemm_nt2_plain / test_gemm_nt2_fused_epilogues: single-term plain 1e-6, single-term extended fp32 outputs 2e-6, split 2e-5
+    (the (hi, lo) sum of a split GELU output 3e-5), bf16 copy 4e-3, column sums 1e-4.  fp16 operands: an fp16 output tensor (the plain
+    kernels' C, the extended epilogue's second copy) element by element within 2^-10 |ref| + 2e-5, the bound of
+    test_decoder_kv_gpu.py::test_memory_side_projection_gemm_fp16; the fp32 outputs of the extended epilogue within 3e-4, the bound
+    test_round5_gpu.py::test_mlp_forward_on_fp16_operands puts on that path."""
+    from spe_amd import kernels as K
+    nt_cases = _nt_cases()
+    M, N, Kd = case["M"], case["N"], case["K"]
+    split, ex, f16, want_T = (bool(case.get(k)) for k in ("split", "ex", "op_f16", "out16T"))
+    plan = K.gemm16_plan(M, N, Kd, **{k: v for k, v in case.items() if k not in "MNK"})
+    name = nt_cases.kernel_name(plan)
+    assert name in nt_cases.INSTANCES
+    g = torch.Generator().manual_seed(M + N + Kd)
+    x = torch.randn(M, Kd, generator=g).to(dev); W = (torch.randn(N, Kd, generator=g) / Kd ** 0.5).to(dev); b = torch.randn(N, generator=g).to(dev)
+    nan = lambda dt=torch.float32: torch.full((M, N), float("nan"), device=dev, dtype=dt)
+    fig = {}
+
+    def h_ok(y, ref):             # fp16 tensor element by element
+        return float(((y.double() - ref).abs() / (2.0 ** -10 * ref.abs() + 2e-5)).max())
+
+    if f16:
+        xh, Wh = K.cvt_f16(x), K.cvt_f16(W)
+        ref = xh.double() @ Wh.double().t() + b.double()
+        if not ex:
+            y = nan(torch.float16)
+            K.gemm16(xh, Wh, y, M, N, Kd, Kd, Kd, N, bias=b, act=0x300)
+            fig["fp16 C / ulp bound"] = (h_ok(y, ref), 1.0)
+        else:                     # fc1 form (pre-activation, GELU as bf16 + fp16 copies), then fc2 form (LayerScale residual)
+            pre, h, hh = nan(), nan(torch.bfloat16), nan(torch.float16)
+            K.gemm16_ex(xh, Wh, M, N, Kd, Kd, Kd, bias=b, C2=pre, out16=h, act=2, out16lo=hh, op_f16=True)
+            gl = torch.nn.functional.gelu(ref)
+            fig["pre"] = (rel(pre, ref), 3e-4); fig["bf16 copy"] = (rel(h.float(), gl), 4e-3); fig["fp16 copy / ulp bound"] = (h_ok(hh, gl), 1.0)
+            res = torch.randn(M, N, generator=g).to(dev); gam = torch.rand(N, generator=g).to(dev); out, y = nan(), nan()
+            K.gemm16_ex(xh, Wh, M, N, Kd, Kd, Kd, bias=b, C=out, C2=y, res=res, rgamma=gam, op_f16=True)
+            fig["y"] = (rel(y, ref), 3e-4); fig["res + gamma y"] = (rel(out, res.double() + gam.double() * ref), 3e-4)
+    else:
+        xh, xl = _split16(x); Wh, Wl = _split16(W)
+        lo = dict(Alo=xl, Blo=Wl) if split else {}
+        seen = x.double() @ W.double().t() if split else xh.double() @ Wh.double().t()
+        ref = seen + b.double()
+        if not ex:
+            C, C2 = nan(), nan()
+            K.gemm16(xh, Wh, C, M, N, Kd, Kd, Kd, N, bias=b, C2=C2, act=1, **lo)
+            tol = 2e-5 if split else 1e-6
+            fig["pre"] = (rel(C2, ref), tol); fig["relu"] = (rel(C, ref.clamp(min=0)), tol)
+        else:
+            tol = 2e-5 if split else 2e-6
+            res = torch.randn(M, N, generator=g).to(dev); gam = torch.rand(N, generator=g).to(dev); out, y, o16 = nan(), nan(), nan(torch.bfloat16)
+            Rp = case.get("ld16t", 0)
+            o16T = torch.full((N, Rp), float("nan"), device=dev).to(torch.bfloat16) if want_T else None
+            K.gemm16_ex(xh, Wh, M, N, Kd, Kd, Kd, bias=b, C=out, C2=y, out16=o16, out16T=o16T, res=res, rgamma=gam, **lo)
+            fig["y"] = (rel(y, ref), tol); fig["res + gamma y"] = (rel(out, res.double() + gam.double() * ref), tol)
+            fig["bf16 copy"] = (rel(o16.float(), ref), 4e-3)                  # out16 = bf16(v), the value before the residual
+            if want_T:            # bit for bit the transpose of the row-major copy, zero beyond row M
+                assert torch.equal(o16T[:, :M], o16.t()) and float(o16T[:, M:].float().abs().sum()) == 0.0
+            if split:             # fc1 form: pre-activation + GELU as a (hi, lo) bf16 pair
+                pre, h, hl = nan(), nan(torch.bfloat16), nan(torch.bfloat16)
+                K.gemm16_ex(xh, Wh, M, N, Kd, Kd, Kd, bias=b, C2=pre, out16=h, out16lo=hl, act=2, **lo)
+                fig["pre"] = (rel(pre, ref), 2e-5); fig["gelu hi + lo"] = (rel(h.float() + hl.float(), torch.nn.functional.gelu(ref)), 3e-5)
+            else:                 # dh form: gelu'(aux), bf16 result, column sums
+                aux = torch.randn(M, N, generator=g).to(dev); d16 = nan(torch.bfloat16); cs = torch.zeros(N, device=dev)
+                K.gemm16_ex(xh, Wh, M, N, Kd, Kd, Kd, out16=d16, colsum=cs, aux=aux, act=2)
+                v = seen * _gelu_prime(aux.double())
+                fig["dh bf16"] = (rel(d16.float(), v), 4e-3); fig["column sums"] = (rel(cs, v.sum(0)), 1e-4)
+    print(f"NTGEMM {_nt_case_id(case)} {name}: " + ", ".join(f"{k} {v:.2e} (< {t:g})" for k, (v, t) in fig.items()))
+    for k, (v, t) in fig.items():
+        assert v < t or (t == 1.0 and v <= t), (k, v, t)
+
+
 @pytest.mark.parametrize("R,Kd,N,act", [(400, 384, 384, 0), (400, 384, 2048, 1), (400, 2048, 384, 0), (400, 384, 96, 2), (1200, 384, 384, 0),
                                         (182, 384, 384, 1), (130, 40, 24, 0), (2047, 200, 136, 2), (600, 776, 392, 0)])
 @pytest.mark.parametrize("prec", ["bf16s", "bf16"])

@@ -732,10 +732,12 @@ def test_criterion_edge_cases_match_oracle(dev, case):
 
 
 @pytest.mark.parametrize("M,N,Kd", [(2100, 384, 1536), (8300, 200, 1024), (2048, 512, 1152), (2051, 64, 4608)])
-def test_gemm_bf16nt_ring(dev, M, N, Kd):
-    """The LDS-DMA ring variant of spe_gemm_bf16nt / _ex (128x64 tiles, taken for M >= 2048, K >= 1024, N <= 512: fc2 forward,
-    fc1 / qkv input gradients) against an fp64 product of the same bf16 values: plain with bias, and the extended epilogue with the
-    LayerScale residual, the pre-residual copy and the bf16 copy.  Ragged M / N exercise the clamped rows of the DMA."""
+def test_gemm_nt2_long_contraction_narrow_output(dev, M, N, Kd):
+    """Long contractions into narrow outputs (M >= 2048, K >= 1024, N <= 512: fc2 forward, fc1 / qkv input gradients) through
+    spe_gemm_bf16nt / _ex.  All four shapes run gemm_nt2_kernel (csrc/gemm_nt2.hip: <64,64,64,2,false,EX,false>, kernels.gemm16_plan says
+    so) - the LDS-DMA variant of gemm_bf16nt_kernel these shapes were written for is gone.  Against an fp64 product of the same bf16
+    values: plain with bias, and the extended epilogue with the LayerScale residual, the pre-residual copy and the bf16 copy.  Ragged
+    M / N exercise the clamped rows of the DMA."""
     from spe_amd import kernels as K
     g_ = torch.Generator().manual_seed(M + N + Kd)
     A = torch.randn(M, Kd, generator=g_).to(dev).to(torch.bfloat16)
