@@ -36,7 +36,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * backward composition - spe_talking_fused(_bits / _plan), spe_attn_merge, spe_talking_flash_rows, spe_talking_flash_dv, spe_talking_bwdq_pass1 removed,
  * spe_talking_stats(_plan) new (the statistics pass alone), spe_rowdot new, spe_layernorm_res_bwd takes dy2.  Still 7 after purely additive
  * entry points: spe_conv_head_fwd / _plan / _bwd and spe_attn_pmean(_dense) (the woct0head backbones' conv class head and patch-affinity CAMs),
- * spe_gemm_bf16nt_plan (the kernel selection of the 16-bit NT GEMM family, host only) - 82 entry points */
+ * spe_gemm_bf16nt_plan / spe_gemm_bf16tn_plan (the kernel selection of the 16-bit NT GEMM family / of the TN weight-gradient GEMM, host only) -
+ * 83 entry points */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -178,6 +179,13 @@ int spe_linear_small_group_bwd(const float* const* dy, const void* x16, const vo
  * the row range (sum them with spe_colsum).  Operands 16-B aligned; lda, ldb, M, N multiples of 8. */
 int spe_gemm_bf16tn(const void* A16, const void* B16, float* C, int M, int N, int R, long lda, long ldb, long ldc,
                     float alpha, int splitk, spe_stream_t stream);
+/* spe_gemm_bf16tn_plan: which instance of gemm_bf16tn_kernel<BM, BN> spe_gemm_bf16tn runs for a problem and how it divides the rows -
+ * the weight gradients of reference models/cait.py:376,390,409 and models/transformer.py:368-425 (see above).  Host only: no device, no
+ * stream, nothing is launched; the launcher calls the same function, so tests and tools can tell which kernel a shape exercises.
+ * v[4] = { BM, BN, splits (grid z), rt_per_split (64-row tiles per split; the last splits may get fewer, or none) }; all zero when M or
+ * N <= 0 (nothing to do).  Returns the status spe_gemm_bf16tn would return, except for the pointer-alignment part of -2: -2 (lda, ldb, M
+ * or N no multiple of 8, splitk > 1), -4 (R <= 0), -5 (more splits than 64-row tiles), else 0. */
+int spe_gemm_bf16tn_plan(int M, int N, int R, long lda, long ldb, int splitk, int* v);
 /* spe_gemm_bf16nt_ex: the same product with an epilogue that feeds the NEXT GEMMs directly (no fp32 round trip, no
  * separate conversion launch):  v = alpha A16 B16^T + bias ; C2 = v (optional) ; v = act(v), or with aux != NULL
  * v = v * act'(aux) (aux [M][ldc]: act 1 = ReLU with the forward output, act 2 = erf-GELU with the pre-activation) ;

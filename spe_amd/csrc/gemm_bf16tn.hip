@@ -172,30 +172,61 @@ static int launch_tn(const GemmTNArgs& p, hipStream_t stream) {
     return 0;
 }
 
-// C-ABI: see include/spe_hip.h (spe_gemm_bf16tn).  -2: unsupported alignment (operands 16-B aligned, lda / ldb / M / N
-// multiples of 8), -5: more splits than 64-row tiles.
-extern "C" int spe_gemm_bf16tn(const void* A16, const void* B16, float* C, int M, int N, int R, long lda, long ldb, long ldc,
-                               float alpha, int splitk, hipStream_t stream) {
-    if (M <= 0 || N <= 0) return 0;
+// The argument checks and the tile choice of spe_gemm_bf16tn, in one place: the launcher switches on the answer, spe_gemm_bf16tn_plan hands
+// it to tests and tools (tests/test_tn_gemm_plan_cpu.py pins it).  Status as the launcher returns it: 1 = nothing to do (M or N <= 0: the
+// launcher returns 0 without a launch), -4: no rows, -2: lda / ldb / M / N not multiples of 8 or splitk > 1, -5: more splits than 64-row tiles.
+struct TnPlan { int BM, BN, splits, rt_per_split; };
+static int tn_gemm_select(int M, int N, int R, long lda, long ldb, int splitk, TnPlan* s) {
+    if (M <= 0 || N <= 0) return 1;
     if (R <= 0) return -4;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (!al16(A16) || !al16(B16) || (lda & 7) || (ldb & 7) || (M & 7) || (N & 7)) return -2;
-    GemmTNArgs p;
-    p.A = reinterpret_cast<const unsigned short*>(A16); p.B = reinterpret_cast<const unsigned short*>(B16); p.C = C;
-    p.M = M; p.N = N; p.R = R; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.alpha = alpha; p.slab = 0;
+    if ((lda & 7) || (ldb & 7) || (M & 7) || (N & 7)) return -2;
     const int rtiles = (R + GT_BR - 1) / GT_BR;
-    if (splitk < 0) { splitk = -splitk; p.slab = (long)M * ldc; if (splitk > rtiles) return -5; }
+    if (splitk < 0) { splitk = -splitk; if (splitk > rtiles) return -5; }
     else if (splitk > 1) return -2;
     if (splitk < 1) splitk = 1;
-    p.splitk = splitk;
-    p.rt_per_split = (rtiles + splitk - 1) / splitk;
+    s->splits = splitk;
+    s->rt_per_split = (rtiles + splitk - 1) / splitk;
     // decoder-size problems (a few hundred rows, no split): 64x64 tiles put 4x the workgroups on the chip (384 x 384: 36 instead of 9)
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128) * splitk;
     static const int small_max = SPE_KNOB("SPE_TN_SMALL_TILES", 256);      // 128-tiles x splits below this: 64 x 64 tiles
     // fewer than half the 512 resident workgroup slots with the wide tiles (a 384 x 384 weight gradient: 9 tiles x 16 splits):
     // 64 x 64 tiles, for which the caller sized the split (kernels.auto_splitk)
-    if (t128 < small_max) return launch_tn<64, 64>(p, stream);
-    if (M > 64 && N > 64) return launch_tn<128, 128>(p, stream);
-    if (M > 64) return launch_tn<128, 64>(p, stream);
-    return launch_tn<64, 64>(p, stream);
+    if (t128 < small_max) { s->BM = 64; s->BN = 64; }
+    else if (M > 64 && N > 64) { s->BM = 128; s->BN = 128; }
+    else if (M > 64) { s->BM = 128; s->BN = 64; }
+    else { s->BM = 64; s->BN = 64; }
+    return 0;
+}
+
+// C-ABI: see include/spe_hip.h (spe_gemm_bf16tn_plan).  Host only: the selection for a problem, no device needed.
+extern "C" int spe_gemm_bf16tn_plan(int M, int N, int R, long lda, long ldb, int splitk, int* v) {
+    TnPlan s;
+    const int rc = tn_gemm_select(M, N, R, lda, ldb, splitk, &s);
+    if (rc < 0) return rc;
+    if (rc > 0) s = TnPlan{0, 0, 0, 0};                                    // nothing to do: no kernel runs
+    if (v) { v[0] = s.BM; v[1] = s.BN; v[2] = s.splits; v[3] = s.rt_per_split; }
+    return 0;
+}
+
+// C-ABI: see include/spe_hip.h (spe_gemm_bf16tn).  -2: unsupported alignment (operands 16-B aligned, lda / ldb / M / N
+// multiples of 8), -5: more splits than 64-row tiles.
+extern "C" int spe_gemm_bf16tn(const void* A16, const void* B16, float* C, int M, int N, int R, long lda, long ldb, long ldc,
+                               float alpha, int splitk, hipStream_t stream) {
+    TnPlan s;
+    const int rc = tn_gemm_select(M, N, R, lda, ldb, splitk, &s);
+    if (rc > 0) return 0;
+    if (rc == -4) return rc;                                               // as before: "no rows" is reported ahead of the pointer check
+    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    if (!al16(A16) || !al16(B16)) return -2;
+    if (rc < 0) return rc;
+    GemmTNArgs p;
+    p.A = reinterpret_cast<const unsigned short*>(A16); p.B = reinterpret_cast<const unsigned short*>(B16); p.C = C;
+    p.M = M; p.N = N; p.R = R; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.alpha = alpha;
+    p.slab = splitk < 0 ? (long)M * ldc : 0;
+    p.splitk = s.splits;
+    p.rt_per_split = s.rt_per_split;
+    if (s.BM == 64 && s.BN == 64) return launch_tn<64, 64>(p, stream);
+    if (s.BM == 128 && s.BN == 128) return launch_tn<128, 128>(p, stream);
+    if (s.BM == 128 && s.BN == 64) return launch_tn<128, 64>(p, stream);
+    return -2;         // unreachable while tn_gemm_select answers with one of the three instances (tests/test_tn_gemm_plan_cpu.py)
 }

@@ -579,6 +579,17 @@ def gemm16_tn(A16, B16, C, M, N, R, lda, ldb, ldc, alpha=1.0, splitk=1):
     return C
 
 
+def gemm16_tn_plan(M, N, R, splitk=1, lda=None, ldb=None):
+    """Which instance gemm16_tn runs for a problem and how it divides the rows (spe_gemm_bf16tn_plan, the launcher's own selection):
+    dict(BM, BN, splits, rt_per_split) - gemm_bf16tn_kernel<BM, BN>, grid z, 64-row tiles per split - or None where gemm16_tn would
+    fail.  Needs no device.  For tests and tools: no hot path calls it."""
+    v = (ctypes.c_int * 4)()
+    rc = lib.load().spe_gemm_bf16tn_plan(M, N, R, M if lda is None else lda, N if ldb is None else ldb, int(splitk), v)
+    if rc != 0:
+        return None
+    return dict(BM=v[0], BN=v[1], splits=v[2], rt_per_split=v[3])
+
+
 def gemm16_ex(A16, B16, M, N, K, lda, ldb, bias=None, C=None, C2=None, out16=None, out16T=None, colsum=None, aux=None,
               alpha=1.0, act=0, res=None, rgamma=None, Alo=None, Blo=None, out16lo=None, drop=None, sscale=None, rps=1, op_f16=False):
     """spe_gemm_bf16nt_ex: v = alpha * A16 @ B16.T + bias; C2 = v; v = act(v) or v * act'(aux); optional fp32 C [M,N], bf16
