@@ -36,8 +36,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * backward composition - spe_talking_fused(_bits / _plan), spe_attn_merge, spe_talking_flash_rows, spe_talking_flash_dv, spe_talking_bwdq_pass1 removed,
  * spe_talking_stats(_plan) new (the statistics pass alone), spe_rowdot new, spe_layernorm_res_bwd takes dy2.  Still 7 after purely additive
  * entry points: spe_conv_head_fwd / _plan / _bwd and spe_attn_pmean(_dense) (the woct0head backbones' conv class head and patch-affinity CAMs),
- * spe_gemm_bf16nt_plan / spe_gemm_bf16tn_plan (the kernel selection of the 16-bit NT GEMM family / of the TN weight-gradient GEMM, host only) -
- * 83 entry points */
+ * spe_gemm_bf16nt_plan / spe_gemm_bf16tn_plan (the kernel selection of the 16-bit NT GEMM family / of the TN weight-gradient GEMM, host only),
+ * spe_pos_learned_fwd / _bwd (the learned position embedding) - 85 entry points */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -525,6 +525,19 @@ int spe_mha_bwd(const void* Qf, const void* Kf, const void* Vf, const void* dOf,
  * mask [B,h,w] uint8 (1 = padded), dim_t[npf] = temperature^(2*(k/2)/npf), out [B,h,w,2*npf] fp32 (row features first). */
 int spe_pos_sine(const void* mask_u8, const float* dim_t, float* out, int B, int h, int w, int npf, float scale,
                  float eps, int normalize, spe_stream_t stream);
+
+/* ---- learned position embedding of the patch grid (reference models/position_encoding.py:60-85: row_embed / col_embed =
+ * nn.Embedding(50, npf), indexed by a cell's row / column; the padding mask is ignored, every image gets the same values).
+ * spe_pos_learned_fwd: col, row [50][npf] -> out [B,h,w,2*npf] fp32, out[b][y][x][c] = col[x][c] for c < npf, row[y][c - npf] above
+ *   (COLUMN features first - the opposite of spe_pos_sine - in the same buffer layout).
+ * spe_pos_learned_bwd (the autograd of the two embedding lookups): g [B,h*w,2*npf] row-major fp32 ->
+ *   d_col[x][c] = sum_b sum_y g[b][y][x][c], d_row[y][c] = sum_b sum_x g[b][y][x][npf + c].  All 50 rows of both [50][npf] gradients are
+ *   OVERWRITTEN (rows >= w / >= h with zeros; the destination needs no zeroing); d_col or d_row NULL: that table is skipped.  One
+ *   workgroup per output row adds its <= 50 B terms in an order fixed by the shape: no atomics, no reduction workspace, bitwise reproducible.
+ * Any npf >= 1 (float4 lanes when npf % 4 == 0 and the pointers are 16-B aligned).  h or w outside 1 .. 50 (the reference's lookup raises
+ * IndexError there), B < 1 or npf < 1: -2, nothing is launched. */
+int spe_pos_learned_fwd(const float* col, const float* row, float* out, int B, int h, int w, int npf, spe_stream_t stream);
+int spe_pos_learned_bwd(const float* g, float* d_col, float* d_row, int B, int h, int w, int npf, spe_stream_t stream);
 
 /* ---- per-class greedy NMS (reference engine_loc.py:154-174: torchvision.ops.nms(boxes, scores, 0.5) per predicted
  * class, results concatenated in ascending class order).  boxes [nimg, nmax, 4] xyxy and labels [nimg, nmax] (int64)

@@ -1668,3 +1668,36 @@ def pos_sine(mask_bool, dim_t, npf, scale, eps, normalize):
     out = torch.empty((B, h, w, 2 * npf), device=mask_bool.device, dtype=torch.float32)
     _call("spe_pos_sine", _p(m8), _p(dim_t), _p(out), B, h, w, npf, float(scale), float(eps), int(bool(normalize)), _st())
     return out
+
+
+POS_TABLE_ROWS = 50        # rows of each learned position table (reference models/position_encoding.py:66-67)
+
+
+def pos_learned_fwd(col, row, B, h, w):
+    """col_embed / row_embed tables [50,npf] -> [B,h,w,2*npf] fp32, column features first (csrc/pos_learned.hip)."""
+    _chk(col, row)
+    npf = col.shape[1]
+    if col.shape != (POS_TABLE_ROWS, npf) or row.shape != col.shape or not (col.is_contiguous() and row.is_contiguous()):
+        raise ValueError(f"pos_learned_fwd: two contiguous [{POS_TABLE_ROWS}, npf] tables expected, got {tuple(col.shape)} and {tuple(row.shape)}")
+    out = torch.empty((B, h, w, 2 * npf), device=col.device, dtype=torch.float32)
+    _call("spe_pos_learned_fwd", _p(col), _p(row), _p(out), B, h, w, npf, _st())
+    return out
+
+
+def pos_learned_bwd(g, B, h, w, npf, need_col=True, need_row=True, dcol_out=None, drow_out=None):
+    """g: contiguous fp32 gradient of pos_learned_fwd's output ([B,h,w,2*npf] or [B,h*w,2*npf]) -> (d_col, d_row), each [50,npf] with every
+    row stored (None when not needed).  dcol_out / drow_out: destinations to write in place (kernels.grad_buffer views; no zeroing needed)."""
+    _chk(g, dcol_out, drow_out)
+    if g.numel() != B * h * w * 2 * npf or not g.is_contiguous():
+        raise ValueError(f"pos_learned_bwd: a contiguous gradient of {B} x {h} x {w} x {2 * npf} elements expected, got {tuple(g.shape)}")
+    outs = []
+    for need, o in ((need_col, dcol_out), (need_row, drow_out)):
+        if not need:
+            o = None
+        elif o is None:
+            o = torch.empty((POS_TABLE_ROWS, npf), device=g.device, dtype=torch.float32)
+        elif o.shape != (POS_TABLE_ROWS, npf) or not o.is_contiguous():
+            raise ValueError(f"pos_learned_bwd: destination {tuple(o.shape)} is not a contiguous [{POS_TABLE_ROWS}, {npf}]")
+        outs.append(o)
+    _call("spe_pos_learned_bwd", _p(g), _p(outs[0]), _p(outs[1]), B, h, w, npf, _st())
+    return outs[0], outs[1]

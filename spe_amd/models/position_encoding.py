@@ -1,12 +1,16 @@
-"""Sine position embedding of the (padded) patch grid - the `position_embedding` the reference attaches to the backbone
-(models/position_encoding.py:21-57, built at :88-92 with N_steps = hidden_dim // 2, normalize=True).  Evaluated by one
-HIP launch (csrc/misc.hip: pos_sine_kernel) on the [B,h,w] padding mask; no parameters, no gradient."""
+"""Position embeddings of the (padded) patch grid - the `position_embedding` the reference attaches to the backbone
+(models/position_encoding.py, built at :88-98 with N_steps = hidden_dim // 2).
+  sine / v2    : PositionEmbeddingSine(normalize=True) (:21-57), one HIP launch (csrc/misc.hip: pos_sine_kernel) on the [B,h,w] padding
+                 mask; no parameters, no gradient.
+  learned / v3 : PositionEmbeddingLearned (:60-85), two [50, N_steps] tables gathered by one HIP launch and differentiated by another
+                 (csrc/pos_learned.hip); grids of at most 50 x 50 cells."""
 import math
 
 import torch
 from torch import nn
 
 from .. import kernels as K
+from .. import ops
 
 
 class PositionEmbeddingSine(nn.Module):
@@ -33,7 +37,35 @@ class PositionEmbeddingSine(nn.Module):
         return feats.permute(0, 3, 1, 2)        # the reference's [B,d,h,w]; the transformer consumes the [B,hw,d] buffer
 
 
+class PositionEmbeddingLearned(nn.Module):
+    """Absolute learned embedding: pos[b, c, y, x] = col_embed[x, c] for c < num_pos_feats, row_embed[y, c - num_pos_feats] above.  The
+    padding mask plays no part: padded cells get embeddings (and send gradients) like any other, every image gets the same values."""
+    TABLE = K.POS_TABLE_ROWS
+
+    def __init__(self, num_pos_feats=256):
+        super().__init__()
+        self.row_embed = nn.Embedding(self.TABLE, num_pos_feats)
+        self.col_embed = nn.Embedding(self.TABLE, num_pos_feats)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.uniform_(self.row_embed.weight)
+        nn.init.uniform_(self.col_embed.weight)
+
+    def forward(self, tensor_list):
+        x = tensor_list.tensors
+        B, (h, w) = x.shape[0], x.shape[-2:]
+        if h > self.TABLE or w > self.TABLE:
+            raise IndexError(f"learned position embedding: a {h} x {w} grid exceeds the {self.TABLE} entries of row_embed / col_embed "
+                             f"(images of at most {16 * self.TABLE} pixels a side at 16-pixel patches); use position_embedding='sine'")
+        feats = ops.pos_learned(self.col_embed.weight, self.row_embed.weight, B, h, w)
+        return feats.permute(0, 3, 1, 2)        # the reference's [B,d,h,w]; the transformer consumes the [B,hw,d] buffer
+
+
 def build_position_encoding(args):
-    if args.position_embedding not in ("v2", "sine"):
-        raise ValueError(f"not supported {args.position_embedding}")
-    return PositionEmbeddingSine(args.hidden_dim // 2, normalize=True)
+    n_steps = args.hidden_dim // 2
+    if args.position_embedding in ("v2", "sine"):
+        return PositionEmbeddingSine(n_steps, normalize=True)
+    if args.position_embedding in ("v3", "learned"):
+        return PositionEmbeddingLearned(n_steps)
+    raise ValueError(f"not supported {args.position_embedding}")

@@ -1251,3 +1251,32 @@ class _BicubicGrid(Function):
 
 def bicubic_grid(pe, gh, gw, h, w):
     return _BicubicGrid.apply(pe, gh, gw, h, w)
+
+
+class _PosLearned(Function):
+    """col_embed / row_embed tables [50,npf] -> position features [B,h,w,2*npf], column features first (reference
+    models/position_encoding.py:74-85; csrc/pos_learned.hip).  The backward sums the incoming gradient over the batch and over the other
+    grid axis into both tables in ONE launch, straight into their all-reduce bucket views; a frozen table is skipped."""
+
+    @staticmethod
+    @K.forward_scope
+    def forward(ctx, col, row, B, h, w):
+        if any(ctx.needs_input_grad[:2]):
+            ctx.g = (B, h, w, col.shape[1])
+            ctx.params = (col, row)
+        return K.pos_learned_fwd(col, row, B, h, w)
+
+    @staticmethod
+    @K.backward_scope
+    def backward(ctx, dy):
+        B, h, w, npf = ctx.g
+        need_c, need_r = ctx.needs_input_grad[:2]
+        colp, rowp = ctx.params
+        dc, dr = K.pos_learned_bwd(dy.contiguous(), B, h, w, npf, need_c, need_r,
+                                   K.grad_buffer(colp) if need_c else None, K.grad_buffer(rowp) if need_r else None)
+        return dc, dr, None, None, None
+
+
+def pos_learned(col, row, B, h, w):
+    """[B,h,w,2*npf] learned position features of an h x w grid (h, w <= 50), the same for every image of the batch."""
+    return _PosLearned.apply(col, row, int(B), int(h), int(w))
