@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void mha_bwd_dkv_kernel(MhaArgs a) {
     __shared__ u32x4m_t sdO[2][MHA_DSV * 64];
     __shared__ uint2 sQ16[2][MHA_DKT * 64];
     __shared__ uint2 sdO16[2][MHA_DVT * 64];
-    __shared__ float sLD[2][32];                           // LSE[16], D[16] of the query tile
+    __shared__ float sLD[2][48];                           // LSE[16], D[16] of the query tile, and what P is at an excluded key [16]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, tid = threadIdx.x;
     const int nkg = (a.ntk + 3) / 4;
     const int kg = blockIdx.x % nkg; const long bh = blockIdx.x / nkg;
@@ -348,9 +348,12 @@ __global__ __launch_bounds__(256) void mha_bwd_dkv_kernel(MhaArgs a) {
         if (tid < dkt * 64) r.c0 = a.Q16[(bh * a.ntq + qt) * dkt * 64 + tid];
         if (tid + 256 < dkt * 64) r.c1 = a.Q16[(bh * a.ntq + qt) * dkt * 64 + tid + 256];
         if (tid < dvt * 64) r.d = a.dO16[(bh * a.ntq + qt) * dvt * 64 + tid];
-        if (tid < 32) {
+        if (tid < 48) {
+            // third block: 0, or NaN for a query without any key (LSE = -inf: every key of the batch padded) - softmax over an empty
+            // set is NaN, as in torch and the materialising path, and dV of that batch is NaN like O, dQ and dK (which D carries there)
             const int qq = min(qt * 16 + (tid & 15), a.Lq - 1);
-            r.e = (tid < 16) ? a.LSE[bh * a.Lq + qq] : a.Dd[bh * a.Lq + qq];
+            const float x = (tid >= 16 && tid < 32) ? a.Dd[bh * a.Lq + qq] : a.LSE[bh * a.Lq + qq];
+            r.e = (tid < 32) ? x : (x == -INFINITY ? __builtin_nanf("") : 0.f);
         }
     };
     auto commit = [&](int buf, const StageRegs& r) {
@@ -359,7 +362,7 @@ __global__ __launch_bounds__(256) void mha_bwd_dkv_kernel(MhaArgs a) {
         if (tid < dkt * 64) sQ16[buf][tid] = r.c0;
         if (tid + 256 < dkt * 64) sQ16[buf][tid + 256] = r.c1;
         if (tid < dvt * 64) sdO16[buf][tid] = r.d;
-        if (tid < 32) sLD[buf][tid] = r.e;
+        if (tid < 48) sLD[buf][tid] = r.e;
     };
     StageRegs sr;
     fetch(0, sr); commit(0, sr);
@@ -385,7 +388,7 @@ __global__ __launch_bounds__(256) void mha_bwd_dkv_kernel(MhaArgs a) {
         for (int r = 0; r < 4; ++r) {
             const bool ok = kv && qb + r < a.Lq;
             const float lse = sLD[buf][4 * (lane >> 4) + r], Dq = sLD[buf][16 + 4 * (lane >> 4) + r];
-            const float p = ok ? __builtin_amdgcn_exp2f(s[r] - lse) : 0.f;
+            const float p = ok ? __builtin_amdgcn_exp2f(s[r] - lse) : sLD[buf][32 + 4 * (lane >> 4) + r];
             const float keep = (a.p_drop > 0.f) ? mha_keep_plain(kbits, lane, r, inv_keep) : 1.f;
             pd[r] = p * keep;
             ds[r] = p * (dp[r] * keep - Dq);
