@@ -37,7 +37,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_talking_stats(_plan) new (the statistics pass alone), spe_rowdot new, spe_layernorm_res_bwd takes dy2.  Still 7 after purely additive
  * entry points: spe_conv_head_fwd / _plan / _bwd and spe_attn_pmean(_dense) (the woct0head backbones' conv class head and patch-affinity CAMs),
  * spe_gemm_bf16nt_plan / spe_gemm_bf16tn_plan (the kernel selection of the 16-bit NT GEMM family / of the TN weight-gradient GEMM, host only),
- * spe_pos_learned_fwd / _bwd (the learned position embedding) - 85 entry points */
+ * spe_pos_learned_fwd / _bwd (the learned position embedding), spe_cam_boxes_device(_workspace) (the CAM pseudo boxes found on the device)
+ * - 87 entry points */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -557,6 +558,22 @@ int spe_nms_sorted(const float* boxes, const long* labels, const int* counts, un
 int spe_cam_prepare(const float* cams, int M, int h, int w, int rows, int cols, float cam_thr, float* minmax,
                     void* out, spe_stream_t stream);
 int spe_cam_contour_boxes(const void* img, int rows, int cols, float area_ratio, int* boxes, int max_boxes, int* nboxes);
+/* spe_cam_boxes_device (device, asynchronous, csrc/cambox_labels.hip): the same boxes in the same order for all M thresholded
+ * images img[M][rows][cols] (uint8, what spe_cam_prepare writes) without leaving the device and without walking a border: two
+ * connected-component labellings of the zero-padded image (foreground 8-connected, background 4-connected; union-find with
+ * atomicMin, label = smallest pixel index), half-unit area counts per 2x2 window and boxes by integer atomics (bitwise
+ * reproducible), every border's count folded into its ancestors in the border tree, the survivors collected per map and
+ * ranked by one workgroup (formulation: csrc/cambox_index.h).
+ * boxes[M][max_boxes][4] int32 [x, y, x+w, y+h], the first nboxes[m] rows of map m valid, the rest untouched; nboxes[m] = -5 when
+ * map m has more than max_boxes survivors (none of its rows is written then), -6 if a label chain overran its bound (not reachable
+ * by a valid image; the kernels give up instead of spinning).  1 <= max_boxes <= 2048.
+ * workspace: caller-owned device memory, 16-B aligned, of at least the bytes spe_cam_boxes_device_workspace reports =
+ * M * (7 * ((rows+2)*(cols+2) rounded up to 4) + 4 + 6 * 2048) * 4; contents need no initialisation.  -2: rows or cols < 1, more than 2^30
+ * padded pixels, M > 65535, max_boxes out of range, workspace misaligned; -4: workspace NULL or too small.  M = 0: nothing launched.
+ * spe_cam_boxes_device_workspace is a host function (bytes: host pointer). */
+int spe_cam_boxes_device_workspace(int M, int rows, int cols, size_t* bytes);
+int spe_cam_boxes_device(const void* img, int M, int rows, int cols, float area_ratio, void* workspace, size_t workspace_bytes,
+                         int* boxes, int* nboxes, int max_boxes, spe_stream_t stream);
 
 /* ---- optimiser step on flat buffers (reference engine.py:161-165: clip_grad_norm_(params, 0.1) + AdamW.step(),
  * parameter groups of main.py:177-191).  spe_sqnorm_partials: partials[b] = sum g^2 over the b-th of nblocks chunks.

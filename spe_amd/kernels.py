@@ -1661,6 +1661,40 @@ def cam_contour_boxes(img_u8_host, area_ratio, max_boxes=256):
     return boxes[:n.value].clone()
 
 
+CAM_MAX_BOXES = 2048       # cap of max_boxes on the device path (csrc/cambox_index.h: LDS of the select kernel)
+
+
+def cam_boxes_workspace_bytes(M, rows, cols):
+    n = ctypes.c_size_t(0)
+    lib.call("spe_cam_boxes_device_workspace", M, rows, cols, ctypes.byref(n))
+    return n.value
+
+
+def cam_boxes_device_packed(imgs_u8_device, area_ratio, max_boxes=256):
+    """cam_boxes_device with both results in ONE int32 device tensor [M * (1 + 4 * max_boxes)]: nboxes [M] first, then
+    boxes [M, max_boxes, 4] - what a caller that wants them on the host copies in one piece."""
+    t = imgs_u8_device
+    if not t.is_cuda:
+        raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    assert t.dtype == torch.uint8 and t.dim() == 3 and t.is_contiguous()
+    M, rows, cols = t.shape
+    out = torch.empty((M * (1 + 4 * max_boxes),), device=t.device, dtype=torch.int32)
+    if M:
+        nbytes = cam_boxes_workspace_bytes(M, rows, cols)
+        ws = torch.empty((nbytes // 4,), device=t.device, dtype=torch.int32)
+        _call("spe_cam_boxes_device", _p(t), M, rows, cols, float(area_ratio), _p(ws), nbytes, _p(out[M:]), _p(out), max_boxes, _st())
+    return out
+
+
+def cam_boxes_device(imgs_u8_device, area_ratio, max_boxes=256):
+    """Thresholded uint8 images on the DEVICE [M, rows, cols] -> (boxes int32 [M, max_boxes, 4] as [x, y, x+w, y+h],
+    nboxes int32 [M]) on the device, asynchronous: the boxes of cam_contour_boxes in the same order, rows >= nboxes[m]
+    unwritten; nboxes[m] < 0 is the status of map m (-5: more than max_boxes).  See csrc/cambox_labels.hip."""
+    M = imgs_u8_device.shape[0]
+    out = cam_boxes_device_packed(imgs_u8_device, area_ratio, max_boxes)
+    return out[M:].view(M, max_boxes, 4), out[:M]
+
+
 def pos_sine(mask_bool, dim_t, npf, scale, eps, normalize):
     """mask [B,h,w] bool (True = padded) -> [B,h,w,2*npf] fp32 sine position features (csrc/misc.hip)."""
     B, h, w = mask_bool.shape
