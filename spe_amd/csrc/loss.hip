@@ -65,9 +65,13 @@ extern "C" int spe_matcher_cost(const float* logits, const float* boxes, const i
 // per image; here the optimum is computed where the costs are, so the criterion needs no device->host round trip
 // and the host keeps running ahead of the GPU).  One wave per (layer, image) problem: the M_b targets of the image
 // are assigned to distinct queries by the shortest-augmenting-path Hungarian algorithm with dual potentials, in
-// fp64 like SciPy (which promotes the fp32 costs to double).  The minimum-cost assignment is unique unless two
-// assignments tie exactly, so the result equals SciPy's.  Output for problem (l, b): M_b triples at offset
-// l*total + toff[b], ordered by query index (the order linear_sum_assignment returns):
+// fp64 like SciPy (which promotes the fp32 costs to double).  Where the minimum-cost assignment is unique the result is
+// SciPy's, pair for pair.  Where two assignments tie exactly it is an equally optimal one, chosen by the lowest-index rule
+// below (targets inserted in order, the lowest free query among equal minima), and SciPy may return another: its scan order
+// differs.  Exact ties are not exotic - jitter_pick_kernel fills picks without a kept candidate with the original box, so
+// one-to-many targets hold exact duplicates and the cost matrix identical columns; every loss is the same for either choice.
+// Output for problem (l, b): M_b triples at offset l*total + toff[b], ordered by query index (the order
+// linear_sum_assignment returns):
 //   srow = (l*B + b)*Q + q        (row of the flattened [L*B*Q] predictions)
 //   gidx = toff[b] + j            (index into the concatenated targets)
 //   lidx = l
@@ -79,7 +83,8 @@ extern "C" int spe_matcher_cost(const float* logits, const float* boxes, const i
 // round 4's kernel, whose butterfly of 64-bit __shfl_xor pairs cost six dependent LDS-crossbar round trips - is two 32-bit unsigned minima
 // over an order-preserving integer image of the doubles, each four DPP stages + four v_readlane, and the lowest column among the ties comes
 // from one ballot per column slot.  No LDS traffic but the cost row, no barrier inside the search.  Same fp64 arithmetic in the same order and
-// the same tie rule (lowest column index) as rounds 2-5: the pairs equal SciPy's at every tested size.
+// the same tie rule (lowest column index) as rounds 2-5: the pairs equal SciPy's wherever the optimum is unique, and are equally optimal
+// where it is not (tests/test_criterion_kernels_gpu.py holds both, and the rule itself, at every CPL and staging boundary).
 #define HUNG_QMAX 1024
 #define HUNG_LDS_FLOATS (36 * 1024)
 
@@ -169,7 +174,7 @@ __global__ __launch_bounds__(64) void hungarian_kernel(const float* __restrict__
             const unsigned lo = hung_wave_umin(((unsigned)(bk >> 32) == hi) ? (unsigned)bk : 0xffffffffu);
             const unsigned long long best = ((unsigned long long)hi << 32) | lo;
             const double delta = hung_unkey(best);
-            // lowest column index among the free columns whose minv equals the minimum (SciPy's tie rule)
+            // lowest column index among the free columns whose minv equals the minimum (this kernel's tie rule, not SciPy's: see above)
             int j1 = 0x7fffffff;
 #pragma unroll
             for (int c = 0; c < CPL; ++c) {

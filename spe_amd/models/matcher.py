@@ -58,7 +58,9 @@ class HungarianMatcher(nn.Module):
         """Device-side assignment for all layers and images at once (csrc/loss.hip: hungarian_kernel): ->
         (srow, gidx int64, lidx int32) device tensors of length L*sum(M_b), ordered (layer, image, query) - the
         flattened form SetCriterion consumes - or None when a problem does not fit the kernel (M_b > Q or Q > 1024;
-        the caller then uses match_many)."""
+        the caller then uses match_many).  The pairs are match_many's (SciPy's) where the optimum is unique; where two
+        assignments tie exactly - duplicated one-to-many targets - they are an equally optimal choice by the kernel's
+        lowest-index rule, which may pair the duplicates differently."""
         L, B, Q, _ = logits.shape
         sizes = [int(len(t["boxes"])) for t in targets]
         if sum(sizes) == 0 or max(sizes) > Q or Q > 1024 or not logits.is_cuda:
