@@ -37,8 +37,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_talking_stats(_plan) new (the statistics pass alone), spe_rowdot new, spe_layernorm_res_bwd takes dy2.  Still 7 after purely additive
  * entry points: spe_conv_head_fwd / _plan / _bwd and spe_attn_pmean(_dense) (the woct0head backbones' conv class head and patch-affinity CAMs),
  * spe_gemm_bf16nt_plan / spe_gemm_bf16tn_plan (the kernel selection of the 16-bit NT GEMM family / of the TN weight-gradient GEMM, host only),
- * spe_pos_learned_fwd / _bwd (the learned position embedding), spe_cam_boxes_device(_workspace) (the CAM pseudo boxes found on the device)
- * - 87 entry points */
+ * spe_pos_learned_fwd / _bwd (the learned position embedding), spe_cam_boxes_device(_workspace) (the CAM pseudo boxes found on the device), spe_voc_match / spe_voc_ap (VOC AP and CorLoc on the device)
+ * - 89 entry points */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -574,6 +574,35 @@ int spe_cam_contour_boxes(const void* img, int rows, int cols, float area_ratio,
 int spe_cam_boxes_device_workspace(int M, int rows, int cols, size_t* bytes);
 int spe_cam_boxes_device(const void* img, int M, int rows, int cols, float area_ratio, void* workspace, size_t workspace_bytes,
                          int* boxes, int* nboxes, int max_boxes, spe_stream_t stream);
+
+/* ---- PASCAL VOC detection metrics (reference engine_loc.py:176-197, datasets/voc_eval.py, datasets/dis_eval.py; csrc/voc_eval.hip).
+ * All arithmetic is fp64 in numpy's operation order, compiled without FMA contraction: with equal inputs the overlaps, and so every
+ * threshold and tie decision, are bit-identical to the reference's.  Asynchronous; integer atomics only (bitwise reproducible).
+ * spe_voc_match: greedy matching of one batch, one wave per (image, class).  Detections of all images concatenated, image i owning
+ *   rows det_off[i] .. det_off[i+1] (int32, device), inside an image ALREADY ordered by (label ascending, score descending) - the order
+ *   spe_nms_sorted's survivors have; det_boxes [nd][4] xyxy in 0-based pixels, det_scores [nd], det_labels [nd] (int64, class = label - 1).
+ *   Ground truth likewise with gt_off [nimg+1]: gt_boxes [ng][4] fp64 in the annotation frame, gt_labels [ng] (int64), gt_difficult [ng].
+ *   score_scale / coord_scale: the decimal round trip of the reference's result files - score -> rint(double(s) * score_scale) / score_scale,
+ *   coordinate -> rint(double(x + 1.0f) * coord_scale) / coord_scale (the + 1 in fp32); 0: the raw double(s), double(x) + 1.0.
+ *   A segment is visited in its incoming order; the overlap (+ 1. widths) is maximised over the ground truth of the class in the image,
+ *   the FIRST maximum wins; ovmax > ovthresh (strict): non-difficult and unused -> tp and used, used -> fp, difficult -> neither;
+ *   otherwise (also without ground truth, or with a NaN overlap) fp.
+ *   flags [nd]: 0 ignored (difficult match, or a label outside 1 .. num_classes), 1 tp, 2 fp; scores_out [nd]: the (quantised) score
+ *   as fp64; every one of the nd entries of both is written.  ADDED into the caller's int32 counters [num_classes]: npos (non-difficult
+ *   ground truth), nimgs (images holding ground truth of the class), hits (CorLoc: the first detection of the segment overlaps ANY
+ *   ground truth of the class, difficult ones included, by more than ovthresh).
+ *   max_det / max_gt: the largest per-image counts in det_off / gt_off (the caller knows them from its shapes); more than 4096 / 1024:
+ *   -2, nothing launched (an image whose offsets exceed them after all is skipped by the kernel).  nimg <= 0: nothing launched.
+ * spe_voc_ap: one workgroup per class over flags sorted per class (class c owning seg_off[c] .. seg_off[c+1], int32, device; inside a
+ *   class in curve order): tp / fp running counts, rec = tp / double(npos[c]), prec = tp / max(tp + fp, DBL_EPSILON), written to
+ *   rec / prec (per detection; NULL: not stored); ap07[c]: the 11-point metric (voc_eval.py:32-40), ap_area[c]: the area under the
+ *   precision envelope (voc_eval.py:41-56; terms added in a fixed order).  No detections: both 0; npos = 0: rec NaN, ap07 0, ap_area NaN. */
+int spe_voc_match(const float* det_boxes, const float* det_scores, const long* det_labels, const int* det_off,
+                  const double* gt_boxes, const long* gt_labels, const unsigned char* gt_difficult, const int* gt_off,
+                  int nimg, int num_classes, int max_det, int max_gt, double ovthresh, double score_scale, double coord_scale,
+                  unsigned char* flags, double* scores_out, int* npos, int* nimgs, int* hits, spe_stream_t stream);
+int spe_voc_ap(const unsigned char* flags, const int* seg_off, const int* npos, int num_classes, double* ap07, double* ap_area,
+               double* rec, double* prec, spe_stream_t stream);
 
 /* ---- optimiser step on flat buffers (reference engine.py:161-165: clip_grad_norm_(params, 0.1) + AdamW.step(),
  * parameter groups of main.py:177-191).  spe_sqnorm_partials: partials[b] = sum g^2 over the b-th of nblocks chunks.

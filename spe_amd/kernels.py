@@ -1735,3 +1735,51 @@ def pos_learned_bwd(g, B, h, w, npf, need_col=True, need_row=True, dcol_out=None
         outs.append(o)
     _call("spe_pos_learned_bwd", _p(g), _p(outs[0]), _p(outs[1]), B, h, w, npf, _st())
     return outs[0], outs[1]
+
+
+# ---- PASCAL VOC detection metrics (csrc/voc_eval.hip) ---------------------------------------------
+VOC_MAX_DET = 4096         # detections / ground-truth boxes per image spe_voc_match takes (-2 beyond)
+VOC_MAX_GT = 1024
+
+
+def voc_match(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_difficult, gt_off, max_det, max_gt,
+              ovthresh, score_scale, coord_scale, npos, nimgs, hits):
+    """Greedy VOC matching of one batch.  Detections [nd,4] fp32 / [nd] fp32 / [nd] int64 and ground truth [ng,4] fp64 / [ng] int64 /
+    [ng] uint8, both concatenated over the images with int32 offsets [nimg+1]; detections ordered by (label asc, score desc) inside
+    an image.  max_det / max_gt: the largest per-image counts (host ints).  Adds into the int32 counters npos / nimgs / hits [C].
+    -> (flags uint8 [nd]: 0 ignored, 1 tp, 2 fp; scores fp64 [nd], quantised when score_scale != 0)."""
+    for t, dt in ((det_boxes, torch.float32), (det_scores, torch.float32), (det_labels, torch.int64), (det_off, torch.int32),
+                  (gt_boxes, torch.float64), (gt_labels, torch.int64), (gt_difficult, torch.uint8), (gt_off, torch.int32),
+                  (npos, torch.int32), (nimgs, torch.int32), (hits, torch.int32)):
+        if not t.is_cuda:
+            raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+        if t.dtype != dt or not t.is_contiguous():
+            raise TypeError(f"voc_match: expected a contiguous {dt} tensor, got {t.dtype}")
+    nd, C, nimg = det_scores.numel(), npos.numel(), det_off.numel() - 1
+    if gt_off.numel() != nimg + 1 or nimgs.numel() != C or hits.numel() != C or det_boxes.numel() != nd * 4 or \
+            det_labels.numel() != nd or gt_boxes.numel() != gt_labels.numel() * 4 or gt_difficult.numel() != gt_labels.numel():
+        raise ValueError("voc_match: inconsistent shapes")
+    flags = torch.empty((nd,), device=det_scores.device, dtype=torch.uint8)
+    scores = torch.empty((nd,), device=det_scores.device, dtype=torch.float64)
+    _call("spe_voc_match", _p(det_boxes), _p(det_scores), _p(det_labels), _p(det_off), _p(gt_boxes), _p(gt_labels), _p(gt_difficult),
+          _p(gt_off), nimg, C, int(max_det), int(max_gt), float(ovthresh), float(score_scale), float(coord_scale), _p(flags),
+          _p(scores), _p(npos), _p(nimgs), _p(hits), _st())
+    return flags, scores
+
+
+def voc_ap(flags, seg_off, npos, want_curve=False):
+    """flags uint8 [nd] sorted per class (class c = seg_off[c] .. seg_off[c+1], int32 [C+1]) in curve order, npos int32 [C]
+    -> (ap07 [C], ap_area [C], rec [nd] or None, prec [nd] or None), fp64 on the device."""
+    for t, dt in ((flags, torch.uint8), (seg_off, torch.int32), (npos, torch.int32)):
+        if not t.is_cuda:
+            raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+        if t.dtype != dt or not t.is_contiguous():
+            raise TypeError(f"voc_ap: expected a contiguous {dt} tensor, got {t.dtype}")
+    C = npos.numel()
+    if seg_off.numel() != C + 1:
+        raise ValueError("voc_ap: seg_off must hold num_classes + 1 offsets")
+    ap = torch.empty((2, C), device=flags.device, dtype=torch.float64)
+    rec = torch.empty((flags.numel(),), device=flags.device, dtype=torch.float64) if want_curve else None
+    prec = torch.empty_like(rec) if want_curve else None
+    _call("spe_voc_ap", _p(flags), _p(seg_off), _p(npos), C, _p(ap[0]), _p(ap[1]), _p(rec), _p(prec), _st())
+    return ap[0], ap[1], rec, prec

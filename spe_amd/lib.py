@@ -11,7 +11,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "spe_hip.h")
 LIBPATH = os.environ.get("SPE_HIP_LIB") or os.path.join(HERE, "libspe_hip.so")
 
 _CTYPES = {
-    "int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float,
+    "int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
     "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "spe_stream_t": ctypes.c_void_p,
 }
 
