@@ -37,8 +37,9 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_talking_stats(_plan) new (the statistics pass alone), spe_rowdot new, spe_layernorm_res_bwd takes dy2.  Still 7 after purely additive
  * entry points: spe_conv_head_fwd / _plan / _bwd and spe_attn_pmean(_dense) (the woct0head backbones' conv class head and patch-affinity CAMs),
  * spe_gemm_bf16nt_plan / spe_gemm_bf16tn_plan (the kernel selection of the 16-bit NT GEMM family / of the TN weight-gradient GEMM, host only),
- * spe_pos_learned_fwd / _bwd (the learned position embedding), spe_cam_boxes_device(_workspace) (the CAM pseudo boxes found on the device), spe_voc_match / spe_voc_ap (VOC AP and CorLoc on the device)
- * - 89 entry points */
+ * spe_pos_learned_fwd / _bwd (the learned position embedding), spe_cam_boxes_device(_workspace) (the CAM pseudo boxes found on the device), spe_voc_match / spe_voc_ap (VOC AP and CorLoc on the device),
+ * spe_resample_plan / _tables / _h / _v (the input transforms: Pillow-exact bilinear resize, crop, flip, normalise, pad)
+ * - 93 entry points */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -603,6 +604,34 @@ int spe_voc_match(const float* det_boxes, const float* det_scores, const long* d
                   unsigned char* flags, double* scores_out, int* npos, int* nimgs, int* hits, spe_stream_t stream);
 int spe_voc_ap(const unsigned char* flags, const int* seg_off, const int* npos, int num_classes, double* ap07, double* ap_area,
                double* rec, double* prec, spe_stream_t stream);
+
+/* ---- input transforms on the device (reference datasets/transforms.py + util/misc.collate_fn; csrc/img_resample.hip).
+ * Pillow's Image.resize(..., BILINEAR) restated bit for bit: per axis, source length inS (after the crop) and output length outS,
+ * in fp64 without FMA contraction: scale = inS / outS, fs = max(scale, 1), support = fs, ksize = (int)ceil(support) * 2 + 1; per
+ * output xx: center = (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0), n = min((int)(center + support + 0.5), inS)
+ * - xmin, w[x] = max(0, 1 - |(x + xmin - center + 0.5) / fs|), normalised by their in-order sum, k[x] = (int)(0.5 + w[x] * 2^22);
+ * out = clamp((2^21 + sum src[xmin + x] * k[x]) >> 22, 0, 255) in 32-bit integers.  Horizontal pass first, into uint8; the
+ * vertical pass reads that uint8.  An unchanged axis gets the taps (2^22, 0): Pillow's copy.
+ * Every launch serves n images, each through RS_DESC = 16 longs of a descriptor table that exists twice with equal content: desc_host
+ * (HOST memory: validated, sizes the grids) and desc_dev (what the kernels read).  Fields: 0 src (device pointer, uint8 [srcH][srcW][3]),
+ * 1 srcW, 2 srcH, 3 x0, 4 y0, 5 cw, 6 ch (the crop box in source pixels), 7 flip (view x -> x0 + (flip ? cw - 1 - x : x), y -> y0 + y:
+ * crop and flip are an index map, never materialised), 8 ow, 9 oh (output size), 10 dst (device pointer, uint8 [oh][ow][3], for the
+ * uint8 epilogue; else 0), and, written by spe_resample_plan: 11 byte offset into tmp, 12 / 13 int offsets of the x / y tables, 14 / 15
+ * ksize of x / y.
+ * Status: -2 empty box / output, a side above 32768, unplanned or inconsistent descriptors, an output larger than the batch;
+ * -3 crop box outside the source; -5 ksize above the tap limit 65 (a 32x downscale; 4x needs 9).  A bad call launches nothing.
+ * spe_resample_plan (host only): validates, fills fields 11 .. 15, totals[5] = bytes of tmp, ints of tables, max ow, max oh, max ch.
+ * spe_resample_tables: xmin[outS], n[outS], k[outS][ksize] of both axes of every image, one launch.
+ * spe_resample_h: view -> planar uint8 tmp [3][ch][ow rounded up to 4] per image.
+ * spe_resample_v: out == NULL: tmp -> the uint8 HWC image dst of every descriptor (feeds another resize).  Else the final epilogue:
+ *   out [n][3][Hmax][Wmax] fp32 = lut[c][byte] (lut: 3 x 256 fp32, ToTensor + Normalize as a table) inside [oh][ow] and 0 outside,
+ *   mask [n][Hmax][Wmax] bytes = 0 inside and 1 outside; every element of both is written.  16-byte stores where the address is
+ *   16-byte aligned, element stores at the unaligned head and tail of a row; Wmax is arbitrary. */
+int spe_resample_plan(long* desc_host, int n, long* totals);
+int spe_resample_tables(const long* desc_host, const long* desc_dev, int n, int* tables, spe_stream_t stream);
+int spe_resample_h(const long* desc_host, const long* desc_dev, int n, const int* tables, unsigned char* tmp, spe_stream_t stream);
+int spe_resample_v(const long* desc_host, const long* desc_dev, int n, const int* tables, const unsigned char* tmp, const float* lut,
+                   float* out, unsigned char* mask, int Hmax, int Wmax, spe_stream_t stream);
 
 /* ---- optimiser step on flat buffers (reference engine.py:161-165: clip_grad_norm_(params, 0.1) + AdamW.step(),
  * parameter groups of main.py:177-191).  spe_sqnorm_partials: partials[b] = sum g^2 over the b-th of nblocks chunks.

@@ -20,7 +20,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # builtin matrix instructions around them must keep their results in ordinary VGPRs (see the file header)
 EXTRA_FLAGS = {"attn_flash_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # voc_eval.hip restates numpy's fp64 overlap: no multiply-add may be contracted into an FMA, or a threshold / tie decision can differ
-               "voc_eval.hip": ["-ffp-contract=off"]}
+               "voc_eval.hip": ["-ffp-contract=off"],
+               # img_resample.hip restates Pillow's fp64 coefficient arithmetic in a fixed operation order
+               "img_resample.hip": ["-ffp-contract=off"]}
 
 
 def flags_for(src):

@@ -1783,3 +1783,55 @@ def voc_ap(flags, seg_off, npos, want_curve=False):
     prec = torch.empty_like(rec) if want_curve else None
     _call("spe_voc_ap", _p(flags), _p(seg_off), _p(npos), C, _p(ap[0]), _p(ap[1]), _p(rec), _p(prec), _st())
     return ap[0], ap[1], rec, prec
+
+
+# ---- input transforms: Pillow-exact bilinear resize, crop, flip, normalise, pad (csrc/img_resample.hip) ----------------------------
+RESAMPLE_MAX_TAPS = 65     # taps per output element spe_resample_* take (-5 beyond): a 32x downscale
+RESAMPLE_DESC = 16         # longs per image descriptor (include/spe_hip.h)
+
+
+def resample_batch(jobs, lut=None, out=None, mask=None):
+    """One batched resize round: three launches (tables, horizontal pass, vertical pass) for all images.
+    jobs: [(src, (x0, y0, cw, ch), flip, (oh, ow)), ...] - src a contiguous uint8 [H,W,3] device tensor, the box in source pixels,
+    the flip applied inside the box.  lut None: -> the resized uint8 [oh,ow,3] images.  Else lut is the 3 x 256 fp32 table and
+    out [n,3,Hmax,Wmax] fp32 / mask [n,Hmax,Wmax] bool are overwritten completely: table values inside [oh,ow], 0.0 / True outside."""
+    n = len(jobs)
+    if n == 0:
+        raise ValueError("resample_batch: no images")
+    dev = jobs[0][0].device
+    for src, _, _, _ in jobs:
+        if not src.is_cuda:
+            raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+        if src.dtype != torch.uint8 or src.ndim != 3 or src.shape[2] != 3 or not src.is_contiguous() or src.device != dev:
+            raise TypeError("resample_batch: expected contiguous uint8 [H,W,3] tensors on one device")
+    final = lut is not None
+    dsts = None
+    if final:
+        for t, dt in ((lut, torch.float32), (out, torch.float32), (mask, torch.bool)):
+            if t is None or not t.is_cuda:
+                raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+            if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise TypeError(f"resample_batch: expected a contiguous {dt} tensor on the images' device")
+        if lut.numel() != 768 or out.ndim != 4 or out.shape[:2] != (n, 3) or mask.shape != (n,) + tuple(out.shape[2:]):
+            raise ValueError("resample_batch: lut [3,256], out [n,3,Hmax,Wmax], mask [n,Hmax,Wmax]")
+    else:
+        dsts = [torch.empty((max(int(oh), 0), max(int(ow), 0), 3), device=dev, dtype=torch.uint8) for _, _, _, (oh, ow) in jobs]
+    desc = torch.zeros((n, RESAMPLE_DESC), dtype=torch.int64)
+    for i, (src, (x0, y0, cw, ch), flip, (oh, ow)) in enumerate(jobs):
+        desc[i, :11] = torch.tensor([src.data_ptr(), src.shape[1], src.shape[0], x0, y0, cw, ch, int(bool(flip)), ow, oh,
+                                     0 if final else dsts[i].data_ptr()], dtype=torch.int64)
+    totals = torch.zeros((5,), dtype=torch.int64)
+    _call("spe_resample_plan", desc.data_ptr(), n, totals.data_ptr())
+    tmp_bytes, table_ints = int(totals[0]), int(totals[1])
+    ddev = desc.to(dev, non_blocking=True)
+    tables = torch.empty((table_ints,), device=dev, dtype=torch.int32)
+    tmp = torch.empty((tmp_bytes,), device=dev, dtype=torch.uint8)
+    st = _st()
+    _call("spe_resample_tables", desc.data_ptr(), _p(ddev), n, _p(tables), st)
+    _call("spe_resample_h", desc.data_ptr(), _p(ddev), n, _p(tables), _p(tmp), st)
+    if final:
+        _call("spe_resample_v", desc.data_ptr(), _p(ddev), n, _p(tables), _p(tmp), _p(lut), _p(out), _p(mask), out.shape[2],
+              out.shape[3], st)
+        return out, mask
+    _call("spe_resample_v", desc.data_ptr(), _p(ddev), n, _p(tables), _p(tmp), None, None, None, 0, 0, st)
+    return dsts
