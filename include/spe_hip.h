@@ -38,8 +38,9 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * entry points: spe_conv_head_fwd / _plan / _bwd and spe_attn_pmean(_dense) (the woct0head backbones' conv class head and patch-affinity CAMs),
  * spe_gemm_bf16nt_plan / spe_gemm_bf16tn_plan (the kernel selection of the 16-bit NT GEMM family / of the TN weight-gradient GEMM, host only),
  * spe_pos_learned_fwd / _bwd (the learned position embedding), spe_cam_boxes_device(_workspace) (the CAM pseudo boxes found on the device), spe_voc_match / spe_voc_ap (VOC AP and CorLoc on the device),
+ * spe_coco_match / spe_coco_accumulate (the COCO AP / AR tables on the device),
  * spe_resample_plan / _tables / _h / _v (the input transforms: Pillow-exact bilinear resize, crop, flip, normalise, pad)
- * - 93 entry points */
+ * - 95 entry points */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -604,6 +605,43 @@ int spe_voc_match(const float* det_boxes, const float* det_scores, const long* d
                   unsigned char* flags, double* scores_out, int* npos, int* nimgs, int* hits, spe_stream_t stream);
 int spe_voc_ap(const unsigned char* flags, const int* seg_off, const int* npos, int num_classes, double* ap07, double* ap_area,
                double* rec, double* prec, spe_stream_t stream);
+
+/* ---- COCO detection metrics (reference engine.evaluate -> datasets/coco_eval.py: COCOeval for iouType 'bbox', useCats = 1;
+ * csrc/coco_eval.hip).  fp64 in COCOeval's operation order, compiled without FMA contraction; asynchronous; integer atomics only.
+ * The parameter arrays are the caller's (numpy's values, uploaded): iou_thrs [10], area_rng [4][2] (lo, hi), rec_thrs [num_rec]
+ * ascending, max_dets [num_max_dets] (int32) - all in device memory.  A flag word holds, for one area range, the matched bits of the 10
+ * thresholds in bits 0 .. 9 and the ignore bits in bits 10 .. 19.
+ * spe_coco_match: greedy matching of one batch, one wave per (image, category).  Detections of all images concatenated, image i owning
+ *   rows det_off[i] .. det_off[i+1] (int32), inside an image ALREADY ordered by (category index ascending, score descending, incoming):
+ *   det_boxes [nd][4] xyxy fp32 in absolute pixels (w = x1 - x0 in fp32, then double; area = w * h in double), det_cats [nd] (int64
+ *   category INDEX 0 .. num_cats-1; anything else belongs to no category).  Ground truth with gt_off [nimg+1]: gt_boxes [ng][4] xywh fp64,
+ *   gt_cats [ng] (int64 index), gt_iscrowd [ng] bytes, gt_area [ng] fp64 (the annotation's field, not w * h).
+ *   IoU of detection D and box G: w = min(D.x + D.w, G.x + G.w) - max(D.x, G.x), h likewise, 0 when either is <= 0, else
+ *   (w * h) / (crowd ? D.area : D.w * D.h + G.w * G.h - w * h).  A box is ignored in area range a when it is crowd or its area is
+ *   < lo or > hi.  Only the first `top` detections of an (image, category) are evaluated (maxDets' last entry).  Per (t, a) and detection:
+ *   best = min(iou_thrs[t], 1 - 1e-10); the non-ignored boxes are walked in incoming order, then - only if none matched - the ignored
+ *   ones; a box already matched at (t, a) is skipped unless it is crowd; iou < best skips, otherwise best = iou and the box is the
+ *   match (so iou == threshold matches and the LAST of equal IoUs wins).  Matched: the ignore bit is the box's; unmatched: the
+ *   detection is ignored when its area is outside the range.
+ *   rank [nd] (int32): position inside the (image, category), or -1 for a detection that is not evaluated (past `top`, or no category);
+ *   words [nd][4] (16-B aligned): the flag words (0 where rank = -1); every entry of both is written.  ADDED into npig [num_cats][4]
+ *   (int32): the non-ignored boxes per category and area range.
+ *   max_det / max_gt: the largest per-image counts; more than 4096 / 512, or top < 1: -2, nothing launched (an image whose offsets exceed
+ *   them after all is skipped by the kernel).  nimg <= 0: nothing launched.
+ * spe_coco_accumulate: one workgroup per (category k, area range a, max_dets entry m) over records sorted per category (category k
+ *   owning seg_off[k] .. seg_off[k+1], int32; inside in curve order: score descending, image id ascending, rank); records with
+ *   rank >= max_dets[m] take no part.  Per threshold t: tp / fp = running counts of the matched / unmatched records that are not ignored,
+ *   rc = tp / npig[k][a], pr = tp / ((fp + tp) + 2^-52), pr made non-increasing from the end, and per rec_thrs[r] the first record with
+ *   rc >= it gives precision [t][r][k][a][m] (the envelope there) and scores [t][r][k][a][m] (its score, widened), 0 past the end;
+ *   recall [t][k][a][m] = the last rc, 0 without records.  npig[k][a] = 0: -1 everywhere.  Every element of the three is written.
+ *   num_rec > 128 or < 1, num_max_dets < 1: -2. */
+int spe_coco_match(const float* det_boxes, const long* det_cats, const int* det_off, const double* gt_boxes, const long* gt_cats,
+                   const unsigned char* gt_iscrowd, const double* gt_area, const int* gt_off, const double* iou_thrs,
+                   const double* area_rng, int nimg, int num_cats, int max_det, int max_gt, int top, int* rank, unsigned* words,
+                   int* npig, spe_stream_t stream);
+int spe_coco_accumulate(const unsigned* words, const int* rank, const float* det_scores, const int* seg_off, const int* npig,
+                        const int* max_dets, const double* rec_thrs, int num_cats, int num_rec, int num_max_dets, double* precision,
+                        double* recall, double* scores, spe_stream_t stream);
 
 /* ---- input transforms on the device (reference datasets/transforms.py + util/misc.collate_fn; csrc/img_resample.hip).
  * Pillow's Image.resize(..., BILINEAR) restated bit for bit: per axis, source length inS (after the crop) and output length outS,

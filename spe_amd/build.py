@@ -21,6 +21,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 EXTRA_FLAGS = {"attn_flash_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # voc_eval.hip restates numpy's fp64 overlap: no multiply-add may be contracted into an FMA, or a threshold / tie decision can differ
                "voc_eval.hip": ["-ffp-contract=off"],
+               # coco_eval.hip restates COCOeval's fp64 IoU the same way: iou == threshold must match, equal IoUs must stay equal
+               "coco_eval.hip": ["-ffp-contract=off"],
                # img_resample.hip restates Pillow's fp64 coefficient arithmetic in a fixed operation order
                "img_resample.hip": ["-ffp-contract=off"]}
 

@@ -1,4 +1,6 @@
-"""PASCAL VOC detection metrics of the SPE evaluation loop: the last step of reference
+"""Detection metrics of the SPE evaluation loops, kept on the device.
+
+PASCAL VOC: the last step of reference
 `engine_loc.evaluate_det_voc` (engine_loc.py:176-197), i.e. `evaluate_detections` -> `voc_eval` (datasets/voc_voc.py:366-437,
 datasets/voc_eval.py) for AP / mAP and `evaluate_discovery` -> `dis_eval` (voc_voc.py:454-488, datasets/dis_eval.py) for CorLoc.
 
@@ -8,6 +10,11 @@ image and class before it, so here the greedy matching runs per batch, straight 
 (`spe_voc_match`: one wave per (image, class)), only flags, scores and integer counters are kept, and `summarize()` is one sort and
 one launch (`spe_voc_ap`: one workgroup per class).  DESIGN.md section 8g has the decomposition, the tie rule and the argument for the
 decimal round trip.
+
+COCO: the last step of reference `engine.evaluate` / `evaluate_refinements` (`CocoEvaluator.update`, `accumulate`, `summarize` of
+datasets/coco_eval.py, i.e. COCOeval for 'bbox').  The same decomposition: `COCODetectionMeter` matches per batch
+(`spe_coco_match`), keeps flag words, ranks and one integer counter, and builds the precision / recall tables once
+(`spe_coco_accumulate`).  DESIGN.md section 8i.
 
 CUDA tensors take the HIP kernels; CPU tensors take a numpy composition of the same rules (the pattern of
 models/conditional_detr.jitter_targets), which is what the host logic, the goldens and the process-group merge are tested with.
@@ -94,6 +101,35 @@ def _ap_host(flags, seg_off, npos, want_curve):
     return t(ap07), t(area), (t(rec_all) if want_curve else None), (t(prec_all) if want_curve else None)
 
 
+def _append_rows(self, new):
+    """Append the rows of `new` to a meter's record columns (self._cols / self._n; capacity grows geometrically)."""
+    n = next(iter(new.values())).shape[0]
+    if self._cols is None or self._n + n > next(iter(self._cols.values())).shape[0]:
+        cap = max(2 * (self._n + n), 4096)                                   # geometric growth
+        grown = {k: torch.empty((cap,) + tuple(v.shape[1:]), dtype=v.dtype, device=v.device) for k, v in new.items()}
+        if self._cols is not None:
+            for k, v in self._cols.items():
+                grown[k][:self._n] = v[:self._n]
+        self._cols = grown
+    for k, v in new.items():
+        self._cols[k][self._n:self._n + n] = v
+    self._n += n
+
+
+def _all_gather_rows(t, world, group):
+    """Rows of every rank, concatenated in rank order (the counts differ: pad to the largest)."""
+    import torch.distributed as dist
+    n = torch.tensor([t.shape[0]], dtype=torch.int64, device=t.device)
+    ns = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(ns, n, group=group)
+    ns = [int(x) for x in ns]
+    pad = torch.zeros((max(max(ns), 1),) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    pad[:t.shape[0]] = t
+    outs = [torch.empty_like(pad) for _ in range(world)]
+    dist.all_gather(outs, pad, group=group)
+    return torch.cat([o[:k] for o, k in zip(outs, ns)])
+
+
 class VOCDetectionMeter:
     """Accumulates VOC AP / mAP and CorLoc over an evaluation run.
 
@@ -125,18 +161,7 @@ class VOCDetectionMeter:
         self._counters = None                  # int32 [3, C]: npos, nimgs, hits
         self._merged = False
 
-    def _append(self, new):
-        n = new["flag"].numel()
-        if self._cols is None or self._n + n > self._cols["flag"].numel():
-            cap = max(2 * (self._n + n), 4096)                                   # geometric growth
-            grown = {k: torch.empty((cap,), dtype=v.dtype, device=v.device) for k, v in new.items()}
-            if self._cols is not None:
-                for k, v in self._cols.items():
-                    grown[k][:self._n] = v[:self._n]
-            self._cols = grown
-        for k, v in new.items():
-            self._cols[k][self._n:self._n + n] = v
-        self._n += n
+    _append = _append_rows
 
     @torch.no_grad()
     def update(self, results, gts):
@@ -204,17 +229,7 @@ class VOCDetectionMeter:
             self._device, self._counters = dev, torch.zeros((3, C), dtype=torch.int32, device=dev)
         world = dist.get_world_size(group)
 
-        def gather(t):
-            n = torch.tensor([t.numel()], dtype=torch.int64, device=dev)
-            ns = [torch.zeros_like(n) for _ in range(world)]
-            dist.all_gather(ns, n, group=group)
-            ns = [int(x) for x in ns]
-            pad = torch.zeros((max(max(ns), 1),), dtype=t.dtype, device=dev)
-            pad[:t.numel()] = t
-            outs = [torch.empty_like(pad) for _ in range(world)]
-            dist.all_gather(outs, pad, group=group)
-            return torch.cat([o[:k] for o, k in zip(outs, ns)])
-
+        gather = lambda t: _all_gather_rows(t, world, group)
         dtypes = {"score": torch.float64, "flag": torch.uint8, "cls": torch.int64, "img": torch.int64, "ord": torch.int32}
         cols = {k: gather(self._cols[k][:self._n] if self._cols is not None else torch.empty((0,), dtype=dt, device=dev))
                 for k, dt in dtypes.items()}
@@ -264,4 +279,275 @@ class VOCDetectionMeter:
             rec, prec, flags = rec.cpu(), prec.cpu(), flags.cpu()
             for k, v in (("rec", rec), ("prec", prec), ("flags", flags)):
                 out[k] = [v[off[c]:off[c + 1]] for c in range(C)]
+        return out
+
+
+# ---- COCO: the AP / AR tables of COCOeval (reference engine.evaluate -> datasets/coco_eval.py) --------------------------------------
+def coco_params():
+    """COCOeval's Params for iouType 'bbox', computed by numpy exactly as published; the device only ever sees these arrays."""
+    return {"iouThrs": np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True),
+            "recThrs": np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True),
+            "maxDets": [1, 10, 100],
+            "areaRng": [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]],
+            "areaRngLbl": ["all", "small", "medium", "large"]}
+
+
+def _coco_match_host(det_boxes, det_cats, det_off, gt_boxes, gt_cats, gt_iscrowd, gt_area, gt_off, iou_thrs, area_rng, max_det, max_gt,
+                     top, npig):
+    """kernels.coco_match on CPU tensors (same arguments, same results, same limits): per (image, category) the detections in order,
+    per detection the IoUs once and the 40 (area range, threshold) walks side by side - the layout of the kernel's lanes."""
+    if max_det > K.COCO_MAX_DET or max_gt > K.COCO_MAX_GT:
+        raise ValueError(f"at most {K.COCO_MAX_DET} detections and {K.COCO_MAX_GT} ground-truth boxes per image")
+    Kc, T, A = npig.shape[0], K.COCO_T, K.COCO_A
+    bx, dc, doff = det_boxes.numpy(), det_cats.numpy(), det_off.numpy()
+    dx, dy = bx[:, 0].astype(np.float64), bx[:, 1].astype(np.float64)
+    dw, dh = (bx[:, 2] - bx[:, 0]).astype(np.float64), (bx[:, 3] - bx[:, 1]).astype(np.float64)      # fp32 differences, widened
+    darea = dw * dh
+    gb, gc, goff = gt_boxes.numpy().reshape(-1, 4), gt_cats.numpy(), gt_off.numpy()
+    crowd_all, area_all = gt_iscrowd.numpy().astype(bool), gt_area.numpy()
+    rng = area_rng.numpy().reshape(A, 2)
+    lo, hi = rng[:, 0], rng[:, 1]
+    thr = np.minimum(iou_thrs.numpy(), 1 - 1e-10)
+    rank = np.full(dc.shape[0], -1, np.int32)
+    words = np.zeros((dc.shape[0], A), np.int32)
+    cnt = np.zeros((Kc, A), np.int32)
+    ai, ti = np.meshgrid(np.arange(A), np.arange(T), indexing="ij")
+    shifts = np.arange(T, dtype=np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for i in range(doff.shape[0] - 1):
+            d0, d1, g0, g1 = doff[i], doff[i + 1], goff[i], goff[i + 1]
+            for c in np.union1d(dc[d0:d1], gc[g0:g1]):
+                if c < 0 or c >= Kc:
+                    continue
+                g = np.nonzero(gc[g0:g1] == c)[0] + g0
+                d = (np.nonzero(dc[d0:d1] == c)[0] + d0)[:top]
+                G = g.size
+                crowd, gx, gy, gw, gh = crowd_all[g], gb[g, 0], gb[g, 1], gb[g, 2], gb[g, 3]
+                ig = crowd[None, :] | (area_all[g][None, :] < lo[:, None]) | (area_all[g][None, :] > hi[:, None])      # [A,G]
+                cnt[c] += (~ig).sum(1).astype(np.int32)
+                gm = np.zeros((A, T, G), bool)
+                for r, j in enumerate(d):
+                    w = np.minimum(dx[j] + dw[j], gx + gw) - np.maximum(dx[j], gx)
+                    h = np.minimum(dy[j] + dh[j], gy + gh) - np.maximum(dy[j], gy)
+                    inter = w * h
+                    o = np.where((w > 0) & (h > 0), inter / np.where(crowd, darea[j], darea[j] + gw * gh - inter), 0.)
+                    best, m = np.broadcast_to(thr, (A, T)).copy(), np.full((A, T), -1)
+                    free = np.ones((A, T), bool)
+                    for group in (False, True):
+                        for q in range(G):
+                            take = (ig[:, q] == group)[:, None] & free & ~(gm[:, :, q] & (not crowd[q])) & ~(o[q] < best)
+                            best[take], m[take] = o[q], q
+                        free = m < 0                       # the ignored group is walked only where nothing matched
+                    dm = m >= 0
+                    dig = np.broadcast_to(((darea[j] < lo) | (darea[j] > hi))[:, None], (A, T))
+                    if G:
+                        dig = np.where(dm, ig[ai, np.maximum(m, 0)], dig)
+                    gm[ai[dm], ti[dm], m[dm]] = True
+                    rank[j] = r
+                    words[j] = ((dm.astype(np.int64) << shifts).sum(1) | (dig.astype(np.int64) << (shifts + T)).sum(1)).astype(np.int32)
+    npig += torch.from_numpy(cnt)
+    return torch.from_numpy(rank), torch.from_numpy(words)
+
+
+def _coco_accumulate_host(words, rank, scores, seg_off, npig, max_dets, rec_thrs):
+    """kernels.coco_accumulate on CPU tensors."""
+    T, A = K.COCO_T, K.COCO_A
+    wd, rk, sc, off = words.numpy(), rank.numpy(), scores.numpy(), seg_off.numpy()
+    npg, lims, thr = npig.numpy(), max_dets.numpy(), rec_thrs.numpy()
+    Kc, M, R = npg.shape[0], lims.size, thr.size
+    precision, recall, score_at = -np.ones((T, R, Kc, A, M)), -np.ones((T, Kc, A, M)), -np.ones((T, R, Kc, A, M))
+    tbits = np.arange(T)[:, None]
+    for k in range(Kc):
+        seg = slice(off[k], off[k + 1])
+        for m in range(M):
+            part = rk[seg] < lims[m]
+            w, s = wd[seg][part], sc[seg][part].astype(np.float64)
+            nd = s.size
+            for a in range(A):
+                if npg[k, a] == 0:
+                    continue
+                mt, ig = ((w[:, a][None, :] >> tbits) & 1).astype(bool), ((w[:, a][None, :] >> (tbits + T)) & 1).astype(bool)
+                tp, fp = np.cumsum(mt & ~ig, axis=1).astype(np.float64), np.cumsum(~mt & ~ig, axis=1).astype(np.float64)
+                rc = tp / npg[k, a]
+                pr = tp / ((fp + tp) + np.spacing(1))
+                env = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]
+                recall[:, k, a, m] = rc[:, -1] if nd else 0
+                for t in range(T):
+                    at = np.searchsorted(rc[t], thr, side="left")
+                    ok = at < nd
+                    precision[t, :, k, a, m] = np.where(ok, env[t][np.minimum(at, max(nd - 1, 0))], 0.) if nd else 0.
+                    score_at[t, :, k, a, m] = np.where(ok, s[np.minimum(at, max(nd - 1, 0))], 0.) if nd else 0.
+    t = torch.from_numpy
+    return t(precision), t(recall), t(score_at)
+
+
+class COCODetectionMeter:
+    """Accumulates the COCO detection metrics over an evaluation run: the twelve numbers of COCOeval.summarize() for 'bbox' and the
+    precision / recall / scores tables behind them (what the reference's CocoEvaluator returns as coco_eval['bbox'].stats / .eval).
+
+        m = COCODetectionMeter(cat_ids)
+        m.update(results, gts)     # per batch, straight after per_class_nms
+        m.merge()                  # once, when the images were split over ranks
+        out = m.summarize()        # {'stats' [12], 'eval': {...}, 'npig' [K,4]}
+
+    results: the list `infer.per_class_nms` returns - per image {'scores' [n] fp32, 'labels' [n] category ids (ids outside cat_ids are
+    dropped), 'boxes' [n,4] xyxy fp32 in absolute pixels}.  gts: per image {'boxes' [g,4] xywh (the annotation's bbox), 'labels' [g],
+    'iscrowd' [g], 'area' [g] (the annotation's own field, not w * h), 'image_id' (int or 0-d tensor)}.
+
+    Inside an (image, category) the detections are matched in descending score, equal scores in their incoming order, the first 100
+    only.  The curve of a category is ordered by score descending, then image id ascending, then that rank - the order COCOeval's stable
+    sort gives its image-sorted lists - so nothing depends on batch order or on how the images were split over ranks.  update() does not
+    read device data on the host.  DESIGN.md section 8i has the rules, the tie order, the limits and what is (not) pinned."""
+
+    def __init__(self, cat_ids):
+        self.cat_ids = sorted({int(c) for c in cat_ids})
+        if not self.cat_ids:
+            raise ValueError("COCODetectionMeter: no categories")
+        self.params = coco_params()
+        self.reset()
+
+    def reset(self):
+        self._device = None
+        self._n, self._cols = 0, None          # records: capacity-sized tensors, the first _n rows valid
+        self._ids = []                         # image ids of every update (images without detections included)
+        self._npig = None                      # int32 [K, 4]
+        self._dev_params = None
+        self._merged = False
+
+    _append = _append_rows
+
+    def _start(self, dev):
+        """First use of a device: the counter and the parameter arrays (numpy's values) in one copy."""
+        P, Kc = self.params, len(self.cat_ids)
+        self._device = dev
+        self._npig = torch.zeros((Kc, K.COCO_A), dtype=torch.int32, device=dev)
+        f = torch.from_numpy(np.concatenate([P["iouThrs"], np.asarray(P["areaRng"], np.float64).reshape(-1), P["recThrs"]]))
+        i = torch.tensor(self.cat_ids + list(P["maxDets"]), dtype=torch.int64)
+        if dev.type == "cuda":
+            f, i = f.pin_memory().to(dev, non_blocking=True), i.pin_memory().to(dev, non_blocking=True)
+        T, A = K.COCO_T, K.COCO_A
+        self._dev_params = {"iouThrs": f[:T], "areaRng": f[T:T + 2 * A], "recThrs": f[T + 2 * A:], "cat_ids": i[:Kc],
+                            "maxDets": i[Kc:].to(torch.int32)}
+
+    def _empty_cols(self, dev):
+        return {"score": torch.empty(0, dtype=torch.float32, device=dev), "words": torch.empty((0, K.COCO_A), dtype=torch.int32, device=dev),
+                "rank": torch.empty(0, dtype=torch.int32, device=dev), "cat": torch.empty(0, dtype=torch.int64, device=dev),
+                "img": torch.empty(0, dtype=torch.int64, device=dev)}
+
+    @torch.no_grad()
+    def update(self, results, gts):
+        if self._merged:
+            raise RuntimeError("COCODetectionMeter: update() after merge(); reset() first")
+        if len(results) != len(gts):
+            raise ValueError("COCODetectionMeter.update: one ground-truth dict per result")
+        if not results:
+            return
+        dev, Kc = results[0]["scores"].device, len(self.cat_ids)
+        if self._device is None:
+            self._start(dev)
+        elif dev != self._device:
+            raise ValueError(f"COCODetectionMeter: tensors on {dev}, earlier updates on {self._device}")
+        nd = [int(r["scores"].shape[0]) for r in results]                       # host lengths: the shapes we are handed
+        ng = [int(g["labels"].shape[0]) for g in gts]
+        if max(nd) > K.COCO_MAX_DET or max(ng) > K.COCO_MAX_GT:
+            raise ValueError(f"at most {K.COCO_MAX_DET} detections and {K.COCO_MAX_GT} ground-truth boxes per image")
+        scores = torch.cat([r["scores"].reshape(-1) for r in results]).float()
+        labels = torch.cat([r["labels"].reshape(-1) for r in results]).long()
+        boxes = torch.cat([r["boxes"].reshape(-1, 4) for r in results]).float()
+        gboxes = torch.cat([g["boxes"].reshape(-1, 4) for g in gts]).to(dev, torch.float64).contiguous()
+        glabels = torch.cat([g["labels"].reshape(-1) for g in gts]).to(dev, torch.int64)
+        gcrowd = torch.cat([g["iscrowd"].reshape(-1) for g in gts]).to(dev).ne(0).to(torch.uint8)
+        garea = torch.cat([g["area"].reshape(-1) for g in gts]).to(dev, torch.float64).contiguous()
+        # offsets, the image of every row and the image ids: what the host knows from the shapes goes up in ONE copy
+        ids = [g["image_id"] for g in gts]
+        ids_dev = None
+        if any(torch.is_tensor(i) for i in ids):
+            ids_dev, ids = torch.stack([torch.as_tensor(i).reshape(()).to(dev, torch.int64) for i in ids]), []
+        nimg, ndt = len(nd), sum(nd)
+        host = torch.from_numpy(np.concatenate([[0], np.cumsum(nd), [0], np.cumsum(ng), np.repeat(np.arange(nimg), nd), ids]).astype(np.int64))
+        if dev.type == "cuda":
+            host = host.pin_memory().to(dev, non_blocking=True)
+        det_off, gt_off = host[:nimg + 1].to(torch.int32), host[nimg + 1:2 * nimg + 2].to(torch.int32)
+        img = host[2 * nimg + 2:2 * nimg + 2 + ndt]
+        ids = ids_dev if ids_dev is not None else host[2 * nimg + 2 + ndt:]
+        self._ids.append(ids)
+        # category id -> index into cat_ids; ids that are not in the list become Kc and gather at the end of the image
+        cid = self._dev_params["cat_ids"]
+
+        def index_of(lab):
+            at = torch.searchsorted(cid, lab).clamp(max=Kc - 1)
+            return torch.where(cid[at] == lab, at, Kc)
+        cat, gcat = index_of(labels), index_of(glabels)
+        # (category ascending, score descending) inside every image, equal scores in incoming order
+        o1 = torch.sort(scores, descending=True, stable=True).indices
+        o2 = torch.sort(img[o1] * (Kc + 1) + cat[o1], stable=True).indices
+        order = o1[o2]
+        scores, cat, boxes = scores[order].contiguous(), cat[order].contiguous(), boxes[order].contiguous()
+        match = K.coco_match if dev.type == "cuda" else _coco_match_host
+        rank, words = match(boxes, cat, det_off, gboxes, gcat, gcrowd, garea, gt_off, self._dev_params["iouThrs"],
+                            self._dev_params["areaRng"], max(nd), max(ng), self.params["maxDets"][-1], self._npig)
+        # a detection that was not evaluated (no category, or past the first 100) moves behind every category
+        self._append({"score": scores, "words": words, "rank": rank, "cat": torch.where(rank < 0, Kc, cat), "img": ids[img]})
+
+    def merge(self, group=None):
+        """Gather the records of every rank and all-reduce npig: afterwards every rank summarizes the whole run.  A no-op without an
+        initialised process group."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        if self._merged:
+            raise RuntimeError("COCODetectionMeter: merge() called twice; reset() first")
+        if self._device is None:                                                # a rank that saw no image
+            self._start(torch.device("cuda" if dist.get_backend(group) == "nccl" else "cpu"))
+        dev, world = self._device, dist.get_world_size(group)
+        mine = {k: v[:self._n] for k, v in self._cols.items()} if self._cols is not None else self._empty_cols(dev)
+        cols = {k: _all_gather_rows(mine[k], world, group) for k in ("score", "words", "rank", "cat", "img")}
+        self._ids = [_all_gather_rows(torch.cat(self._ids) if self._ids else torch.empty((0,), dtype=torch.int64, device=dev), world, group)]
+        self._cols, self._n = cols, cols["rank"].shape[0]
+        dist.all_reduce(self._npig, group=group)
+        self._merged = True
+
+    @torch.no_grad()
+    def summarize(self, return_records=False):
+        """-> {'stats': the twelve numbers of COCOeval.summarize() (fp64 [12]: AP, AP50, AP75, AP small / medium / large at maxDets 100; AR at
+        maxDets 1 / 10 / 100, AR small / medium / large at 100), 'eval': {'params', 'counts' [T,R,K,A,M], 'precision' [T,R,K,A,M], 'recall'
+        [T,K,A,M], 'scores' [T,R,K,A,M]} as COCOeval.eval holds them (-1: no ground truth to find), 'npig' int32 [K,4]} - numpy arrays.
+        return_records adds 'records': 'cat' (index into cat_ids), 'img', 'rank', 'score', 'words' [n,4] of the evaluated detections, per
+        category in curve order."""
+        if self._npig is None:
+            raise RuntimeError("COCODetectionMeter.summarize: nothing accumulated")
+        ids = torch.sort(torch.cat(self._ids)).values
+        if bool((ids[1:] == ids[:-1]).any()):
+            raise ValueError("COCODetectionMeter: an image id was accumulated twice")
+        dev, n, Kc, P = self._device, self._n, len(self.cat_ids), self.params
+        col = {k: v[:n] for k, v in self._cols.items()} if self._cols is not None else self._empty_cols(dev)
+        # curve order by stable sorts, last key first: category, score descending, image id, rank
+        o = torch.sort(col["rank"], stable=True).indices
+        o = o[torch.sort(col["img"][o], stable=True).indices]
+        o = o[torch.sort(col["score"][o], descending=True, stable=True).indices]
+        o = o[torch.sort(col["cat"][o], stable=True).indices]
+        col = {k: v[o].contiguous() for k, v in col.items()}
+        seg_off = torch.searchsorted(col["cat"], torch.arange(Kc + 1, device=dev)).to(torch.int32)     # category Kc: not evaluated, behind
+        acc = K.coco_accumulate if dev.type == "cuda" else _coco_accumulate_host
+        precision, recall, scores = acc(col["words"], col["rank"], col["score"], seg_off, self._npig.contiguous(),
+                                        self._dev_params["maxDets"], self._dev_params["recThrs"])
+        precision, recall, scores = precision.cpu().numpy(), recall.cpu().numpy(), scores.cpu().numpy()
+
+        def one(ap, iou_thr=None, area="all", max_dets=100):                    # COCOeval._summarize, on the host
+            a, m = P["areaRngLbl"].index(area), P["maxDets"].index(max_dets)
+            s = precision[:, :, :, a, m] if ap else recall[:, :, a, m]
+            if iou_thr is not None:
+                s = s[np.where(iou_thr == P["iouThrs"])[0]]
+            return -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
+        d1, d10, d100 = P["maxDets"]
+        stats = np.array([one(1, max_dets=d100), one(1, .5, max_dets=d100), one(1, .75, max_dets=d100), one(1, area="small", max_dets=d100),
+                          one(1, area="medium", max_dets=d100), one(1, area="large", max_dets=d100), one(0, max_dets=d1),
+                          one(0, max_dets=d10), one(0, max_dets=d100), one(0, area="small", max_dets=d100),
+                          one(0, area="medium", max_dets=d100), one(0, area="large", max_dets=d100)], np.float64)
+        out = {"stats": stats, "npig": self._npig.cpu().numpy().copy(),
+               "eval": {"params": {**P, "catIds": list(self.cat_ids)}, "counts": [K.COCO_T, len(P["recThrs"]), Kc, K.COCO_A, len(P["maxDets"])],
+                        "precision": precision, "recall": recall, "scores": scores}}
+        if return_records:
+            end = int(seg_off[-1])
+            out["records"] = {k: v[:end].cpu().numpy() for k, v in col.items()}
         return out

@@ -1785,6 +1785,61 @@ def voc_ap(flags, seg_off, npos, want_curve=False):
     return ap[0], ap[1], rec, prec
 
 
+# ---- COCO detection metrics (csrc/coco_eval.hip) ---------------------------------------------------
+COCO_MAX_DET = 4096        # detections / ground-truth boxes per image spe_coco_match takes (-2 beyond)
+COCO_MAX_GT = 512
+COCO_T, COCO_A = 10, 4     # IoU thresholds and area ranges a flag word is laid out for
+COCO_MAX_REC = 128         # recall thresholds spe_coco_accumulate takes (-2 beyond)
+
+
+def _coco_check(name, pairs):
+    for t, dt in pairs:
+        if not t.is_cuda:
+            raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+        if t.dtype != dt or not t.is_contiguous():
+            raise TypeError(f"{name}: expected a contiguous {dt} tensor, got {t.dtype}")
+
+
+def coco_match(det_boxes, det_cats, det_off, gt_boxes, gt_cats, gt_iscrowd, gt_area, gt_off, iou_thrs, area_rng, max_det, max_gt,
+               top, npig):
+    """Greedy COCO matching of one batch.  Detections [nd,4] fp32 xyxy / [nd] int64 category index and ground truth [ng,4] fp64 xywh /
+    [ng] int64 index / [ng] uint8 iscrowd / [ng] fp64 area, both concatenated over the images with int32 offsets [nimg+1]; detections
+    ordered by (category, score descending, incoming) inside an image.  iou_thrs fp64 [10], area_rng fp64 [4,2]: the caller's numpy values
+    on the device.  max_det / max_gt: the largest per-image counts (host ints); top: maxDets' last entry.  Adds into npig int32 [K,4].
+    -> (rank int32 [nd]: position inside the (image, category), -1 not evaluated; words int32 [nd,4]: per area range the matched bits of
+    the 10 thresholds in bits 0 .. 9 and the ignore bits in bits 10 .. 19)."""
+    _coco_check("coco_match", ((det_boxes, torch.float32), (det_cats, torch.int64), (det_off, torch.int32), (gt_boxes, torch.float64),
+                               (gt_cats, torch.int64), (gt_iscrowd, torch.uint8), (gt_area, torch.float64), (gt_off, torch.int32),
+                               (iou_thrs, torch.float64), (area_rng, torch.float64), (npig, torch.int32)))
+    nd, ng, nimg = det_cats.numel(), gt_cats.numel(), det_off.numel() - 1
+    if gt_off.numel() != nimg + 1 or det_boxes.numel() != nd * 4 or gt_boxes.numel() != ng * 4 or gt_iscrowd.numel() != ng or \
+            gt_area.numel() != ng or iou_thrs.numel() != COCO_T or area_rng.numel() != 2 * COCO_A or npig.dim() != 2 or \
+            npig.shape[1] != COCO_A:
+        raise ValueError("coco_match: inconsistent shapes")
+    rank = torch.empty((nd,), device=det_cats.device, dtype=torch.int32)
+    words = torch.empty((nd, COCO_A), device=det_cats.device, dtype=torch.int32)
+    _call("spe_coco_match", _p(det_boxes), _p(det_cats), _p(det_off), _p(gt_boxes), _p(gt_cats), _p(gt_iscrowd), _p(gt_area), _p(gt_off),
+          _p(iou_thrs), _p(area_rng), nimg, npig.shape[0], int(max_det), int(max_gt), int(top), _p(rank), _p(words), _p(npig), _st())
+    return rank, words
+
+
+def coco_accumulate(words, rank, scores, seg_off, npig, max_dets, rec_thrs):
+    """Records sorted per category (category k = seg_off[k] .. seg_off[k+1], int32 [K+1]) in curve order: words int32 [n,4], rank int32
+    [n], scores fp32 [n]; npig int32 [K,4], max_dets int32 [M], rec_thrs fp64 [R] ascending
+    -> (precision [10,R,K,4,M], recall [10,K,4,M], scores [10,R,K,4,M]), fp64 on the device, COCOeval's layouts, -1 where npig = 0."""
+    _coco_check("coco_accumulate", ((words, torch.int32), (rank, torch.int32), (scores, torch.float32), (seg_off, torch.int32),
+                                    (npig, torch.int32), (max_dets, torch.int32), (rec_thrs, torch.float64)))
+    n, Kc, M, R = rank.numel(), npig.shape[0], max_dets.numel(), rec_thrs.numel()
+    if words.numel() != n * COCO_A or scores.numel() != n or seg_off.numel() != Kc + 1 or npig.dim() != 2 or npig.shape[1] != COCO_A:
+        raise ValueError("coco_accumulate: inconsistent shapes")
+    prec = torch.empty((COCO_T, R, Kc, COCO_A, M), device=rank.device, dtype=torch.float64)
+    rec = torch.empty((COCO_T, Kc, COCO_A, M), device=rank.device, dtype=torch.float64)
+    sco = torch.empty_like(prec)
+    _call("spe_coco_accumulate", _p(words), _p(rank), _p(scores), _p(seg_off), _p(npig), _p(max_dets), _p(rec_thrs), Kc, R, M,
+          _p(prec), _p(rec), _p(sco), _st())
+    return prec, rec, sco
+
+
 # ---- input transforms: Pillow-exact bilinear resize, crop, flip, normalise, pad (csrc/img_resample.hip) ----------------------------
 RESAMPLE_MAX_TAPS = 65     # taps per output element spe_resample_* take (-5 beyond): a 32x downscale
 RESAMPLE_DESC = 16         # longs per image descriptor (include/spe_hip.h)
