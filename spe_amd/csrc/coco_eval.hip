@@ -8,23 +8,14 @@
 // them.  Everything is fp64 in the operation order of COCOeval; the file is compiled with -ffp-contract=off (spe_amd/build.py
 // EXTRA_FLAGS), so no multiply-add of the IoU is contracted into an FMA and every threshold and tie decision is the host's, bit for
 // bit.  Counters are 32-bit integer atomics; there are no floating-point atomics and nothing synchronises the host.
-#include "common.h"
+// The limits, the segment search, the compaction step and the workgroup primitives are det_eval_common.h's, shared with voc_eval.hip.
+#include "det_eval_common.h"
 #include <float.h>
 
-#define COCO_MAXDET 4096     // detections per image (the convention of spe_nms_sorted and spe_voc_match)
 #define COCO_MAXGT 512       // ground-truth boxes per image: what one wave keeps in LDS
 #define COCO_T 10            // IoU thresholds: the matched / ignore bit fields of a flag word are 10 wide
 #define COCO_A 4             // area ranges: one flag word each
 #define COCO_MAXR 128        // recall thresholds spe_coco_accumulate takes (COCOeval has 101)
-
-// first index in [lo, hi) whose category is >= v (categories ascending inside an image)
-__device__ __forceinline__ int coco_lower_bound(const long* __restrict__ cat, int lo, int hi, long v) {
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (cat[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // One wave per (image, category).  The category's ground truth of the image is compacted into LDS in its incoming order.  The
 // detections of the segment are visited in order; per visit the IoUs are computed ONCE, one box per lane, into LDS, and then lane
@@ -46,7 +37,7 @@ __global__ __launch_bounds__(64) void coco_match_kernel(const float* __restrict_
     __shared__ unsigned char gf[COCO_MAXGT];            // bit a: ignored in area range a; bit 4: crowd
     const int img = blockIdx.x / K, c = blockIdx.x - img * K, lane = threadIdx.x;
     const int d0 = det_off[img], d1 = det_off[img + 1], g0 = gt_off[img], g1 = gt_off[img + 1];
-    if (d1 - d0 < 0 || d1 - d0 > COCO_MAXDET || g1 - g0 < 0 || g1 - g0 > COCO_MAXGT) return;    // the entry point refuses these (-2)
+    if (d1 - d0 < 0 || d1 - d0 > EV_MAXDET || g1 - g0 < 0 || g1 - g0 > COCO_MAXGT) return;      // the entry point refuses these (-2)
     const double r00 = area_rng[0], r01 = area_rng[1], r10 = area_rng[2], r11 = area_rng[3];
     const double r20 = area_rng[4], r21 = area_rng[5], r30 = area_rng[6], r31 = area_rng[7];
 
@@ -62,14 +53,12 @@ __global__ __launch_bounds__(64) void coco_match_kernel(const float* __restrict_
                 ((unsigned)(crowd || ar < r20 || ar > r21) << 2) | ((unsigned)(crowd || ar < r30 || ar > r31) << 3) |
                 ((unsigned)crowd << 4);
         }
-        const unsigned long long mask = __ballot(m);
+        const int p = ev_compact_slot(m, lane, ng);
         if (m) {
-            const int p = ng + __popcll(mask & ((1ull << lane) - 1ull));
             gb[p][0] = gt_box[(long)j * 4]; gb[p][1] = gt_box[(long)j * 4 + 1];
             gb[p][2] = gt_box[(long)j * 4 + 2]; gb[p][3] = gt_box[(long)j * 4 + 3];
             gf[p] = (unsigned char)f; gm[p] = 0ull;
         }
-        ng += __popcll(mask);
         n0 += __popcll(__ballot(m && !(f & 1u))); n1 += __popcll(__ballot(m && !(f & 2u)));
         n2 += __popcll(__ballot(m && !(f & 4u))); n3 += __popcll(__ballot(m && !(f & 8u)));
     }
@@ -79,7 +68,8 @@ __global__ __launch_bounds__(64) void coco_match_kernel(const float* __restrict_
     }
     __syncthreads();
 
-    const int s = coco_lower_bound(det_cat, d0, d1, (long)c), e = coco_lower_bound(det_cat, s, d1, (long)c + 1);
+    int s, e;
+    ev_segment(det_cat, d0, d1, (long)c, s, e);
     const int ev = min(e, s + top);
     // categories outside 0 .. K-1 belong to nobody and detections past the first `top` of a segment are never evaluated: rank -1
     if (c == 0) for (int i = d0 + lane; i < s; i += 64) { rank[i] = -1; *(uint4*)(words + (long)i * 4) = make_uint4(0u, 0u, 0u, 0u); }
@@ -147,7 +137,7 @@ extern "C" int spe_coco_match(const float* det_boxes, const long* det_cats, cons
                               const double* iou_thrs, const double* area_rng, int nimg, int num_cats, int max_det, int max_gt,
                               int top, int* rank, unsigned* words, int* npig, hipStream_t st) {
     if (nimg <= 0) return 0;
-    if (num_cats < 1 || max_det < 0 || max_gt < 0 || max_det > COCO_MAXDET || max_gt > COCO_MAXGT || top < 1 ||
+    if (num_cats < 1 || max_det < 0 || max_gt < 0 || max_det > EV_MAXDET || max_gt > COCO_MAXGT || top < 1 ||
         (long)nimg * num_cats > 0x7fffffffL)
         return -2;
     hipLaunchKernelGGL(coco_match_kernel, dim3((unsigned)(nimg * num_cats)), dim3(64), 0, st, det_boxes, det_cats, det_off, gt_boxes,
@@ -157,57 +147,6 @@ extern "C" int spe_coco_match(const float* det_boxes, const long* det_cats, cons
 }
 
 // ---- precision / recall tables of one (category, area range, maxDets entry) per workgroup ------------------------------------------
-#define ACC_THREADS 256
-// inclusive sum over the workgroup of (tp count | fp count << 16) - at most 256 of each per chunk; total: the chunk's sum
-__device__ __forceinline__ int acc_scan(int v, int* ws, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
-    __syncthreads();
-    if (lane == 63) ws[w] = v;
-    __syncthreads();
-    int off = 0; total = 0;
-#pragma unroll
-    for (int k = 0; k < ACC_THREADS / 64; ++k) { if (k < w) off += ws[k]; total += ws[k]; }
-    return v + off;
-}
-// v -> max over the threads >= this one (the precision envelope inside a chunk); total: the chunk's maximum
-__device__ __forceinline__ double acc_suffix_max(double v, double* ws, double& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const double t = __shfl_down(v, o, 64); if (lane + o < 64) v = fmax(v, t); }
-    __syncthreads();
-    if (lane == 0) ws[w] = v;
-    __syncthreads();
-    total = ws[0];
-#pragma unroll
-    for (int k = 1; k < ACC_THREADS / 64; ++k) { if (k > w) v = fmax(v, ws[k]); total = fmax(total, ws[k]); }
-    return v;
-}
-// sum (or minimum) over the workgroup, integers: order-free
-__device__ __forceinline__ int acc_isum(int v, int* ws) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int r = ws[0];
-#pragma unroll
-    for (int k = 1; k < ACC_THREADS / 64; ++k) r += ws[k];
-    return r;
-}
-__device__ __forceinline__ int acc_imin(int v, int* ws) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int r = ws[0];
-#pragma unroll
-    for (int k = 1; k < ACC_THREADS / 64; ++k) r = min(r, ws[k]);
-    return r;
-}
-
 // Records of category k: seg_off[k] .. seg_off[k+1], in curve order (score descending, image id ascending, rank).  A record takes
 // part when its rank is below the maxDets entry; COCOeval removes the others before its cumulative sums, here they stay in place and
 // add to neither count (their precision enters the envelope as 0 and no look-up may land on them).  Per threshold t: a forward pass
@@ -216,14 +155,14 @@ __device__ __forceinline__ int acc_imin(int v, int* ws) {
 // running maximum from the end, and np.searchsorted(rc, recThrs, side='left') is turned round: rc only grows at a true positive, so
 // the first record with rc >= thr is a true positive (or the first record of all, for the thresholds its rc already reaches) and
 // that record writes the thresholds in (rc before it, its rc].  Every threshold is written by at most one record.
-__global__ __launch_bounds__(ACC_THREADS) void coco_accumulate_kernel(const unsigned* __restrict__ words, const int* __restrict__ rank,
+__global__ __launch_bounds__(EV_THREADS) void coco_accumulate_kernel(const unsigned* __restrict__ words, const int* __restrict__ rank,
                                                                       const float* __restrict__ score, const int* __restrict__ seg_off,
                                                                       const int* __restrict__ npig, const int* __restrict__ max_dets,
                                                                       const double* __restrict__ rec_thrs, int K, int R, int M,
                                                                       double* __restrict__ precision, double* __restrict__ recall,
                                                                       double* __restrict__ scores) {
-    __shared__ int iws[ACC_THREADS / 64];
-    __shared__ double dws[ACC_THREADS / 64];
+    __shared__ int iws[EV_THREADS / 64];
+    __shared__ double dws[EV_THREADS / 64];
     __shared__ double thr[COCO_MAXR], pbuf[COCO_MAXR], sbuf[COCO_MAXR];
     const int tid = threadIdx.x;
     const int m = blockIdx.x % M, a = (blockIdx.x / M) % COCO_A, k = blockIdx.x / (M * COCO_A);
@@ -233,20 +172,20 @@ __global__ __launch_bounds__(ACC_THREADS) void coco_accumulate_kernel(const unsi
     const long kam = ((long)k * COCO_A + a) * M + m;                        // [T,R,K,A,M] and [T,K,A,M]: the trailing three
     const long KAM = (long)K * COCO_A * M;
     if (np_i == 0) {                                                        // COCOeval skips the category: its init value stays
-        for (int q = tid; q < COCO_T * R; q += ACC_THREADS) { precision[(long)q * KAM + kam] = -1.; scores[(long)q * KAM + kam] = -1.; }
+        for (int q = tid; q < COCO_T * R; q += EV_THREADS) { precision[(long)q * KAM + kam] = -1.; scores[(long)q * KAM + kam] = -1.; }
         if (tid < COCO_T) recall[(long)tid * KAM + kam] = -1.;
         return;
     }
     const double npd = (double)np_i;
-    for (int r = tid; r < R; r += ACC_THREADS) thr[r] = rec_thrs[r];
+    for (int r = tid; r < R; r += EV_THREADS) thr[r] = rec_thrs[r];
     const unsigned* wd = words + s * 4 + a;
     const int* rk = rank + s;
     const float* sc = score + s;
 
     for (int t = 0; t < COCO_T; ++t) {
-        for (int r = tid; r < R; r += ACC_THREADS) { pbuf[r] = 0.; sbuf[r] = 0.; }
+        for (int r = tid; r < R; r += EV_THREADS) { pbuf[r] = 0.; sbuf[r] = 0.; }
         int ltp = 0, lfp = 0, lfirst = n;
-        for (int i = tid; i < n; i += ACC_THREADS) {
+        for (int i = tid; i < n; i += EV_THREADS) {
             if (rk[i] < lim) {
                 const unsigned w = wd[(long)i * 4];
                 const bool mt = (w >> t) & 1u, ig = (w >> (COCO_T + t)) & 1u;
@@ -254,12 +193,12 @@ __global__ __launch_bounds__(ACC_THREADS) void coco_accumulate_kernel(const unsi
                 lfirst = min(lfirst, i);
             }
         }
-        int ctp = acc_isum(ltp, iws), cfp = acc_isum(lfp, iws);
-        const int first = acc_imin(lfirst, iws);
+        int ctp = ev_isum(ltp, iws), cfp = ev_isum(lfp, iws);
+        const int first = ev_imin(lfirst, iws);
         const int ttp = ctp;
 
         double env = 0.;
-        for (int base = n > 0 ? (n - 1) / ACC_THREADS * ACC_THREADS : -1; base >= 0; base -= ACC_THREADS) {
+        for (int base = n > 0 ? (n - 1) / EV_THREADS * EV_THREADS : -1; base >= 0; base -= EV_THREADS) {
             const int i = base + tid;
             const bool valid = i < n && rk[i] < lim;
             bool istp = false, isfp = false;
@@ -269,11 +208,11 @@ __global__ __launch_bounds__(ACC_THREADS) void coco_accumulate_kernel(const unsi
                 istp = mt && !ig; isfp = !mt && !ig;
             }
             int tot;
-            const int inc = acc_scan((int)istp | ((int)isfp << 16), iws, tot);
+            const int inc = ev_scan((int)istp | ((int)isfp << 16), iws, tot);
             const int tp = ctp - (tot & 0xffff) + (inc & 0xffff), fp = cfp - (tot >> 16) + (inc >> 16);
             const double p = valid ? (double)tp / (((double)fp + (double)tp) + DBL_EPSILON) : 0.;      // np.spacing(1) = 2^-52
             double cmax;
-            const double en = fmax(acc_suffix_max(p, dws, cmax), env);
+            const double en = fmax(ev_suffix_max(p, dws, cmax), env);
             if (valid && (istp || i == first)) {
                 const double rc = (double)tp / npd;
                 int r = 0;
@@ -290,7 +229,7 @@ __global__ __launch_bounds__(ACC_THREADS) void coco_accumulate_kernel(const unsi
             ctp -= tot & 0xffff; cfp -= tot >> 16;
         }
         __syncthreads();
-        for (int r = tid; r < R; r += ACC_THREADS) {
+        for (int r = tid; r < R; r += EV_THREADS) {
             precision[((long)t * R + r) * KAM + kam] = pbuf[r];
             scores[((long)t * R + r) * KAM + kam] = sbuf[r];
         }
@@ -305,7 +244,7 @@ extern "C" int spe_coco_accumulate(const unsigned* words, const int* rank, const
                                    double* precision, double* recall, double* scores, hipStream_t st) {
     if (num_cats <= 0) return 0;
     if (num_rec < 1 || num_rec > COCO_MAXR || num_max_dets < 1 || (long)num_cats * COCO_A * num_max_dets > 0x7fffffffL) return -2;
-    hipLaunchKernelGGL(coco_accumulate_kernel, dim3((unsigned)(num_cats * COCO_A * num_max_dets)), dim3(ACC_THREADS), 0, st, words,
+    hipLaunchKernelGGL(coco_accumulate_kernel, dim3((unsigned)(num_cats * COCO_A * num_max_dets)), dim3(EV_THREADS), 0, st, words,
                        rank, det_scores, seg_off, npig, max_dets, rec_thrs, num_cats, num_rec, num_max_dets, precision, recall, scores);
     SPE_CHECK_LAUNCH();
     return 0;

@@ -8,10 +8,10 @@
 // (spe_amd/build.py EXTRA_FLAGS): no multiply-add of the overlap is contracted into an FMA, so with equal inputs the overlaps - and
 // with them every threshold and tie decision - are bit-identical to numpy's.  Counters are 32-bit integer atomics (order-free, bitwise
 // reproducible); there are no floating-point atomics and nothing synchronises the host.
-#include "common.h"
+// The limits, the segment search, the compaction step and the workgroup primitives are det_eval_common.h's, shared with coco_eval.hip.
+#include "det_eval_common.h"
 #include <float.h>
 
-#define VOC_MAXDET 4096      // detections per image (the convention of spe_nms_sorted)
 #define VOC_MAXGT 1024       // ground-truth boxes per image: what one workgroup keeps in LDS
 
 // The decimal round trip of the reference's result files (voc_voc.py:383-386): '{:.3f}' of the score, '{:.1f}' of the fp32
@@ -23,15 +23,6 @@ __device__ __forceinline__ double voc_score(float s, double scale) {
 }
 __device__ __forceinline__ double voc_coord(float x, double scale) {
     return scale != 0.0 ? rint((double)(x + 1.0f) * scale) / scale : (double)x + 1.0;
-}
-
-// first index in [lo, hi) whose label is >= v (labels ascending inside an image)
-__device__ __forceinline__ int voc_lower_bound(const long* __restrict__ lab, int lo, int hi, long v) {
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (lab[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // One wave per (image, class).  The class's ground truth of the image is compacted into LDS in its incoming order (so "lowest index"
@@ -48,7 +39,7 @@ __global__ __launch_bounds__(64) void voc_match_kernel(const float* __restrict__
     __shared__ unsigned char gd[VOC_MAXGT], used[VOC_MAXGT];
     const int img = blockIdx.x / C, c = blockIdx.x - img * C, lane = threadIdx.x;
     const int d0 = det_off[img], d1 = det_off[img + 1], g0 = gt_off[img], g1 = gt_off[img + 1];
-    if (d1 - d0 < 0 || d1 - d0 > VOC_MAXDET || g1 - g0 < 0 || g1 - g0 > VOC_MAXGT) return;      // the entry point refuses these (-2)
+    if (d1 - d0 < 0 || d1 - d0 > EV_MAXDET || g1 - g0 < 0 || g1 - g0 > VOC_MAXGT) return;       // the entry point refuses these (-2)
     const long want = (long)c + 1;
 
     int ng = 0, nnd = 0;                                                                        // wave-uniform
@@ -56,14 +47,12 @@ __global__ __launch_bounds__(64) void voc_match_kernel(const float* __restrict__
         const int j = base + lane;
         const bool m = j < g1 && gt_label[j] == want;
         const bool df = m && gt_diff[j] != 0;
-        const unsigned long long mask = __ballot(m);
+        const int p = ev_compact_slot(m, lane, ng);
         if (m) {
-            const int p = ng + __popcll(mask & ((1ull << lane) - 1ull));
             gb[p][0] = gt_box[(long)j * 4]; gb[p][1] = gt_box[(long)j * 4 + 1];
             gb[p][2] = gt_box[(long)j * 4 + 2]; gb[p][3] = gt_box[(long)j * 4 + 3];
             gd[p] = df; used[p] = 0;
         }
-        ng += __popcll(mask);
         nnd += __popcll(__ballot(m && !df));
     }
     if (lane == 0) {
@@ -72,7 +61,8 @@ __global__ __launch_bounds__(64) void voc_match_kernel(const float* __restrict__
     }
     __syncthreads();
 
-    const int s = voc_lower_bound(det_label, d0, d1, want), e = voc_lower_bound(det_label, s, d1, want + 1);
+    int s, e;
+    ev_segment(det_label, d0, d1, want, s, e);
     // labels outside 1 .. C belong to no class (engine_loc.py:184): flag 0, written by the first / last wave of the image
     if (c == 0) for (int i = d0 + lane; i < s; i += 64) { flag[i] = 0; score_out[i] = voc_score(det_score[i], sscale); }
     if (c == C - 1) for (int i = e + lane; i < d1; i += 64) { flag[i] = 0; score_out[i] = voc_score(det_score[i], sscale); }
@@ -120,7 +110,7 @@ extern "C" int spe_voc_match(const float* det_boxes, const float* det_scores, co
                              double coord_scale, unsigned char* flags, double* scores_out, int* npos, int* nimgs, int* hits,
                              hipStream_t st) {
     if (nimg <= 0) return 0;
-    if (num_classes < 1 || max_det < 0 || max_gt < 0 || max_det > VOC_MAXDET || max_gt > VOC_MAXGT ||
+    if (num_classes < 1 || max_det < 0 || max_gt < 0 || max_det > EV_MAXDET || max_gt > VOC_MAXGT ||
         (long)nimg * num_classes > 0x7fffffffL)
         return -2;
     hipLaunchKernelGGL(voc_match_kernel, dim3((unsigned)(nimg * num_classes)), dim3(64), 0, st, det_boxes, det_scores, det_labels,
@@ -131,52 +121,12 @@ extern "C" int spe_voc_match(const float* det_boxes, const float* det_scores, co
 }
 
 // ---- precision / recall curve and both APs of one class per workgroup ---------------------------------------------------------
-#define AP_THREADS 256
-// inclusive sum over the workgroup of (tp count | fp count << 16) - at most 256 of each per chunk; total: the chunk's sum
-__device__ __forceinline__ int ap_scan(int v, int* ws, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
-    __syncthreads();
-    if (lane == 63) ws[w] = v;
-    __syncthreads();
-    int off = 0; total = 0;
-#pragma unroll
-    for (int k = 0; k < AP_THREADS / 64; ++k) { if (k < w) off += ws[k]; total += ws[k]; }
-    return v + off;
-}
-// v -> max over the threads >= this one (the precision envelope inside a chunk); total: the chunk's maximum
-__device__ __forceinline__ double ap_suffix_max(double v, double* ws, double& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const double t = __shfl_down(v, o, 64); if (lane + o < 64) v = fmax(v, t); }
-    __syncthreads();
-    if (lane == 0) ws[w] = v;
-    __syncthreads();
-    total = ws[0];
-#pragma unroll
-    for (int k = 1; k < AP_THREADS / 64; ++k) { if (k > w) v = fmax(v, ws[k]); total = fmax(total, ws[k]); }
-    return v;
-}
-// sum over the workgroup in an order fixed by the thread layout: xor butterfly per wave, then the waves in index order
-__device__ __forceinline__ double ap_sum(double v, double* ws) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = ws[0];
-#pragma unroll
-    for (int k = 1; k < AP_THREADS / 64; ++k) r += ws[k];
-    return r;
-}
-
-__global__ __launch_bounds__(AP_THREADS) void voc_ap_kernel(const unsigned char* __restrict__ flag, const int* __restrict__ seg_off,
+__global__ __launch_bounds__(EV_THREADS) void voc_ap_kernel(const unsigned char* __restrict__ flag, const int* __restrict__ seg_off,
                                                             const int* __restrict__ npos, double* __restrict__ ap07,
                                                             double* __restrict__ ap_area, double* __restrict__ rec,
                                                             double* __restrict__ prec) {
-    __shared__ int iws[AP_THREADS / 64];
-    __shared__ double dws[AP_THREADS / 64];
+    __shared__ int iws[EV_THREADS / 64];
+    __shared__ double dws[EV_THREADS / 64];
     const int c = blockIdx.x, tid = threadIdx.x;
     const long s = seg_off[c];
     const long n = max((long)seg_off[c + 1] - s, 0l);
@@ -188,11 +138,11 @@ __global__ __launch_bounds__(AP_THREADS) void voc_ap_kernel(const unsigned char*
     double pm[11];
 #pragma unroll
     for (int k = 0; k < 11; ++k) pm[k] = 0.;
-    for (long base = 0; base < n; base += AP_THREADS) {
+    for (long base = 0; base < n; base += EV_THREADS) {
         const long i = base + tid;
         const int f = i < n ? fl[i] : 0;
         int tot;
-        const int inc = ap_scan((f == 1) | ((f == 2) << 16), iws, tot);
+        const int inc = ev_scan((f == 1) | ((f == 2) << 16), iws, tot);
         if (i < n) {
             const int tp = ctp + (inc & 0xffff), fp = cfp + (inc >> 16);
             const double r = (double)tp / np_, p = (double)tp / fmax((double)tp + (double)fp, DBL_EPSILON);
@@ -206,7 +156,7 @@ __global__ __launch_bounds__(AP_THREADS) void voc_ap_kernel(const unsigned char*
     double ap = 0.;
     for (int k = 0; k < 11; ++k) {                                          // a maximum does not depend on the order it is taken in
         double t;
-        ap_suffix_max(pm[k], dws, t);
+        ev_suffix_max(pm[k], dws, t);
         ap = ap + t / 11.;
     }
     if (tid == 0) ap07[c] = ap;
@@ -217,21 +167,21 @@ __global__ __launch_bounds__(AP_THREADS) void voc_ap_kernel(const unsigned char*
     double area = 0.;
     if (1. != last) area = (1. - last) * 0.;                                // the sentinel term: 0, or the NaN numpy gets from rec = NaN / inf
     double env = 0.;
-    for (long base = n > 0 ? (n - 1) / AP_THREADS * AP_THREADS : -1; base >= 0; base -= AP_THREADS) {
+    for (long base = n > 0 ? (n - 1) / EV_THREADS * EV_THREADS : -1; base >= 0; base -= EV_THREADS) {
         const long i = base + tid;
         const int f = i < n ? fl[i] : 0;
         int tot;
-        const int inc = ap_scan((f == 1) | ((f == 2) << 16), iws, tot);
+        const int inc = ev_scan((f == 1) | ((f == 2) << 16), iws, tot);
         const int tp = ctp - (tot & 0xffff) + (inc & 0xffff), fp = cfp - (tot >> 16) + (inc >> 16);
         const double p = i < n ? (double)tp / fmax((double)tp + (double)fp, DBL_EPSILON) : 0.;
         double cmax;
-        const double m = fmax(ap_suffix_max(p, dws, cmax), env);
+        const double m = fmax(ev_suffix_max(p, dws, cmax), env);
         double term = 0.;
         if (i < n) {
             const double r = (double)tp / np_, rp = i > 0 ? (double)(tp - (f == 1)) / np_ : 0.;
             if (r != rp) term = (r - rp) * m;
         }
-        area += ap_sum(term, dws);
+        area += ev_sum(term, dws);
         env = fmax(env, cmax);
         ctp -= tot & 0xffff; cfp -= tot >> 16;
     }
@@ -242,7 +192,7 @@ __global__ __launch_bounds__(AP_THREADS) void voc_ap_kernel(const unsigned char*
 extern "C" int spe_voc_ap(const unsigned char* flags, const int* seg_off, const int* npos, int num_classes, double* ap07,
                           double* ap_area, double* rec, double* prec, hipStream_t st) {
     if (num_classes <= 0) return 0;
-    hipLaunchKernelGGL(voc_ap_kernel, dim3((unsigned)num_classes), dim3(AP_THREADS), 0, st, flags, seg_off, npos, ap07, ap_area,
+    hipLaunchKernelGGL(voc_ap_kernel, dim3((unsigned)num_classes), dim3(EV_THREADS), 0, st, flags, seg_off, npos, ap07, ap_area,
                        rec, prec);
     SPE_CHECK_LAUNCH();
     return 0;

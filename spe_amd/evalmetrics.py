@@ -16,6 +16,9 @@ datasets/coco_eval.py, i.e. COCOeval for 'bbox').  The same decomposition: `COCO
 (`spe_coco_match`), keeps flag words, ranks and one integer counter, and builds the precision / recall tables once
 (`spe_coco_accumulate`).  DESIGN.md section 8i.
 
+What the two have in common - record columns, the single upload of a batch, the batch and curve orders, the process-group merge -
+is `_DetectionMeter`; the matching rules, the host restatements and the result builders are each meter's own.
+
 CUDA tensors take the HIP kernels; CPU tensors take a numpy composition of the same rules (the pattern of
 models/conditional_detr.jitter_targets), which is what the host logic, the goldens and the process-group merge are tested with.
 """
@@ -101,21 +104,6 @@ def _ap_host(flags, seg_off, npos, want_curve):
     return t(ap07), t(area), (t(rec_all) if want_curve else None), (t(prec_all) if want_curve else None)
 
 
-def _append_rows(self, new):
-    """Append the rows of `new` to a meter's record columns (self._cols / self._n; capacity grows geometrically)."""
-    n = next(iter(new.values())).shape[0]
-    if self._cols is None or self._n + n > next(iter(self._cols.values())).shape[0]:
-        cap = max(2 * (self._n + n), 4096)                                   # geometric growth
-        grown = {k: torch.empty((cap,) + tuple(v.shape[1:]), dtype=v.dtype, device=v.device) for k, v in new.items()}
-        if self._cols is not None:
-            for k, v in self._cols.items():
-                grown[k][:self._n] = v[:self._n]
-        self._cols = grown
-    for k, v in new.items():
-        self._cols[k][self._n:self._n + n] = v
-    self._n += n
-
-
 def _all_gather_rows(t, world, group):
     """Rows of every rank, concatenated in rank order (the counts differ: pad to the largest)."""
     import torch.distributed as dist
@@ -130,7 +118,129 @@ def _all_gather_rows(t, world, group):
     return torch.cat([o[:k] for o, k in zip(outs, ns)])
 
 
-class VOCDetectionMeter:
+class _DetectionMeter:
+    """What the two meters share: the record columns, the single host -> device copy of a batch, the two orders (of a batch, of the
+    curves) and the process-group merge.  A subclass declares _SCHEMA (record column -> (dtype, trailing shape)) and _MAX_GT, provides
+    _start(dev) - the first use of a device: self._device and the int32 counter tensor self._counters - and keeps its own matching and
+    its own result builder."""
+    _SCHEMA, _MAX_GT = {}, 0
+
+    def reset(self):
+        self._device = None
+        self._n, self._cols = 0, None          # records: capacity-sized tensors, the first _n rows valid
+        self._ids = []                         # image ids of every update (images without detections included)
+        self._counters = None                  # int32, on the device: what merge() all-reduces
+        self._merged = False
+
+    def _records(self):
+        """The valid rows of every column (views; empty columns before the first record)."""
+        if self._cols is None:
+            return {k: torch.empty((0,) + shape, dtype=dt, device=self._device) for k, (dt, shape) in self._SCHEMA.items()}
+        return {k: self._cols[k][:self._n] for k in self._SCHEMA}
+
+    def _append(self, new):
+        n = new[next(iter(self._SCHEMA))].shape[0]
+        if self._cols is None or self._n + n > next(iter(self._cols.values())).shape[0]:
+            cap, old = max(2 * (self._n + n), 4096), self._cols               # geometric growth
+            self._cols = {k: torch.empty((cap,) + shape, dtype=dt, device=self._device) for k, (dt, shape) in self._SCHEMA.items()}
+            for k, v in (old or {}).items():
+                self._cols[k][:self._n] = v[:self._n]
+        for k in self._SCHEMA:
+            self._cols[k][self._n:self._n + n] = new[k]
+        self._n += n
+
+    def _collect(self, results, gts, gt_fields, pos=False):
+        """The checks of update(), the concatenations and the ONE copy (from pinned memory, asynchronous on the device path) of what the
+        host knows from the shapes - offsets, the image of every row, with `pos` its position inside the image - and of the image ids.
+        gt_fields: ground-truth key -> torch.uint8 (a flag) or torch.float64.  -> None for an empty batch, else the named tensors."""
+        name = type(self).__name__
+        if self._merged:
+            raise RuntimeError(f"{name}: update() after merge(); reset() first")
+        if len(results) != len(gts):
+            raise ValueError(f"{name}.update: one ground-truth dict per result")
+        if not results:
+            return None
+        dev = results[0]["scores"].device
+        if self._device is None:
+            self._start(dev)
+        elif dev != self._device:
+            raise ValueError(f"{name}: tensors on {dev}, earlier updates on {self._device}")
+        nd = [int(r["scores"].shape[0]) for r in results]                       # host lengths: the shapes we are handed
+        ng = [int(g["labels"].shape[0]) for g in gts]
+        if max(nd) > K.MAX_DET or max(ng) > self._MAX_GT:
+            raise ValueError(f"at most {K.MAX_DET} detections and {self._MAX_GT} ground-truth boxes per image")
+        b = {"max_det": max(nd), "max_gt": max(ng),
+             "scores": torch.cat([r["scores"].reshape(-1) for r in results]).float(),
+             "labels": torch.cat([r["labels"].reshape(-1) for r in results]).long(),
+             "boxes": torch.cat([r["boxes"].reshape(-1, 4) for r in results]).float(),
+             "gboxes": torch.cat([g["boxes"].reshape(-1, 4) for g in gts]).to(dev, torch.float64).contiguous(),
+             "glabels": torch.cat([g["labels"].reshape(-1) for g in gts]).to(dev, torch.int64)}
+        for k, dt in gt_fields.items():
+            v = torch.cat([g[k].reshape(-1) for g in gts])
+            b[k] = v.to(dev).ne(0).to(torch.uint8) if dt == torch.uint8 else v.to(dev, dt).contiguous()
+        ids = [g["image_id"] for g in gts]
+        ids_dev = None
+        if any(torch.is_tensor(i) for i in ids):
+            ids_dev, ids = torch.stack([torch.as_tensor(i).reshape(()).to(dev, torch.int64) for i in ids]), []
+        parts = {"det_off": np.concatenate([[0], np.cumsum(nd)]), "gt_off": np.concatenate([[0], np.cumsum(ng)]),
+                 "img": np.repeat(np.arange(len(nd)), nd)}
+        if pos:
+            parts["pos"] = np.concatenate([np.arange(n) for n in nd])
+        parts["ids"] = ids
+        host = torch.from_numpy(np.concatenate(list(parts.values())).astype(np.int64))
+        if dev.type == "cuda":
+            host = host.pin_memory().to(dev, non_blocking=True)
+        b.update(zip(parts, host.split([len(p) for p in parts.values()])))
+        for k in ("det_off", "gt_off") + (("pos",) if pos else ()):
+            b[k] = b[k].to(torch.int32)
+        if ids_dev is not None:
+            b["ids"] = ids_dev
+        self._ids.append(b["ids"])
+        return b
+
+    @staticmethod
+    def _order_batch(scores, img, cls, nkeys):
+        """(cls ascending, score descending) inside every image, equal scores in incoming order; per_class_nms output already is."""
+        o1 = torch.sort(scores, descending=True, stable=True).indices
+        o2 = torch.sort(img[o1] * nkeys + cls[o1], stable=True).indices
+        return o1[o2]
+
+    def merge(self, group=None):
+        """Gather the records of every rank and all-reduce the counters: afterwards every rank summarizes the whole run.  A no-op
+        without an initialised process group."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        if self._merged:
+            raise RuntimeError(f"{type(self).__name__}: merge() called twice; reset() first")
+        if self._device is None:                                                # a rank that saw no image
+            self._start(torch.device("cuda" if dist.get_backend(group) == "nccl" else "cpu"))
+        dev, world = self._device, dist.get_world_size(group)
+        self._cols = {k: _all_gather_rows(v, world, group) for k, v in self._records().items()}
+        self._n = next(iter(self._cols.values())).shape[0]
+        self._ids = [_all_gather_rows(torch.cat(self._ids) if self._ids else torch.empty((0,), dtype=torch.int64, device=dev), world, group)]
+        dist.all_reduce(self._counters, group=group)
+        self._merged = True
+
+    def _check_run(self):
+        if self._counters is None:
+            raise RuntimeError(f"{type(self).__name__}.summarize: nothing accumulated")
+        ids = torch.sort(torch.cat(self._ids)).values
+        if bool((ids[1:] == ids[:-1]).any()):
+            raise ValueError(f"{type(self).__name__}: an image id was accumulated twice")
+
+    def _curve_order(self, keys, ngroups, want):
+        """Curve order by stable sorts, last key first (keys[-1]: the class / category, then 'score' descending, then the rest ascending).
+        -> (the columns `want` in that order, seg_off int32 [ngroups + 1]); records of group `ngroups` (dropped ones) lie behind."""
+        col = self._records()
+        o = torch.sort(col[keys[0]], stable=True).indices
+        for k in keys[1:]:
+            o = o[torch.sort(col[k][o], descending=k == "score", stable=True).indices]
+        col = {k: col[k][o].contiguous() for k in want}
+        return col, torch.searchsorted(col[keys[-1]], torch.arange(ngroups + 1, device=self._device)).to(torch.int32)
+
+
+class VOCDetectionMeter(_DetectionMeter):
     """Accumulates VOC AP / mAP and CorLoc over an evaluation run.
 
         m = VOCDetectionMeter(num_classes=20, ovthresh=0.5, file_roundtrip=True)
@@ -154,89 +264,29 @@ class VOCDetectionMeter:
         self.num_classes, self.ovthresh, self.file_roundtrip = int(num_classes), float(ovthresh), bool(file_roundtrip)
         self.reset()
 
-    def reset(self):
-        self._device = None
-        self._n, self._cols = 0, None          # records: capacity-sized tensors, the first _n rows valid
-        self._ids = []                         # image ids of every update (images without detections included)
-        self._counters = None                  # int32 [3, C]: npos, nimgs, hits
-        self._merged = False
+    _SCHEMA = {"score": (torch.float64, ()), "flag": (torch.uint8, ()), "cls": (torch.int64, ()), "img": (torch.int64, ()),
+               "ord": (torch.int32, ())}
+    _MAX_GT = K.VOC_MAX_GT
 
-    _append = _append_rows
+    def _start(self, dev):
+        self._device, self._counters = dev, torch.zeros((3, self.num_classes), dtype=torch.int32, device=dev)      # npos, nimgs, hits
 
     @torch.no_grad()
     def update(self, results, gts):
-        if self._merged:
-            raise RuntimeError("VOCDetectionMeter: update() after merge(); reset() first")
-        if len(results) != len(gts):
-            raise ValueError("VOCDetectionMeter.update: one ground-truth dict per result")
-        if not results:
+        b = self._collect(results, gts, {"difficult": torch.uint8}, pos=True)
+        if b is None:
             return
-        dev, C = results[0]["scores"].device, self.num_classes
-        if self._device is None:
-            self._device = dev
-            self._counters = torch.zeros((3, C), dtype=torch.int32, device=dev)
-        elif dev != self._device:
-            raise ValueError(f"VOCDetectionMeter: tensors on {dev}, earlier updates on {self._device}")
-        nd = [int(r["scores"].shape[0]) for r in results]                       # host lengths: the shapes we are handed
-        ng = [int(g["labels"].shape[0]) for g in gts]
-        if max(nd) > K.VOC_MAX_DET or max(ng) > K.VOC_MAX_GT:
-            raise ValueError(f"at most {K.VOC_MAX_DET} detections and {K.VOC_MAX_GT} ground-truth boxes per image")
-        scores = torch.cat([r["scores"].reshape(-1) for r in results]).float()
-        labels = torch.cat([r["labels"].reshape(-1) for r in results]).long()
-        boxes = torch.cat([r["boxes"].reshape(-1, 4) for r in results]).float()
-        gboxes = torch.cat([g["boxes"].reshape(-1, 4) for g in gts]).to(dev, torch.float64).contiguous()
-        glabels = torch.cat([g["labels"].reshape(-1) for g in gts]).to(dev, torch.int64)
-        gdiff = torch.cat([g["difficult"].reshape(-1) for g in gts]).to(dev).ne(0).to(torch.uint8)
-        # what the host knows from the shapes - offsets, the image of every row and its position inside the image - and the image ids
-        # go up in ONE copy (from pinned memory, asynchronous on the device path)
-        ids = [g["image_id"] for g in gts]
-        ids_dev = None
-        if any(torch.is_tensor(i) for i in ids):
-            ids_dev, ids = torch.stack([torch.as_tensor(i).reshape(()).to(dev, torch.int64) for i in ids]), []
-        nimg, ndt = len(nd), sum(nd)
-        host = torch.from_numpy(np.concatenate([[0], np.cumsum(nd), [0], np.cumsum(ng), np.repeat(np.arange(nimg), nd)]
-                                               + [np.arange(n) for n in nd] + [ids]).astype(np.int64))
-        if dev.type == "cuda":
-            host = host.pin_memory().to(dev, non_blocking=True)
-        det_off, gt_off = host[:nimg + 1].to(torch.int32), host[nimg + 1:2 * nimg + 2].to(torch.int32)
-        img, pos = host[2 * nimg + 2:2 * nimg + 2 + ndt], host[2 * nimg + 2 + ndt:2 * nimg + 2 + 2 * ndt].to(torch.int32)
-        ids = ids_dev if ids_dev is not None else host[2 * nimg + 2 + 2 * ndt:]
-        self._ids.append(ids)
-        # (label ascending, score descending) inside every image, equal scores in incoming order; per_class_nms output already
-        # is.  Labels outside 1 .. C gather at the two ends of the image.
+        C, labels = self.num_classes, b["labels"]
+        # labels outside 1 .. C gather at the two ends of the image
         cls = torch.where((labels >= 1) & (labels <= C), labels, torch.where(labels < 1, 0, C + 1))
-        o1 = torch.sort(scores, descending=True, stable=True).indices
-        o2 = torch.sort(img[o1] * (C + 2) + cls[o1], stable=True).indices
-        order = o1[o2]
-        scores, cls, boxes = scores[order].contiguous(), cls[order].contiguous(), boxes[order].contiguous()
-        match = K.voc_match if dev.type == "cuda" else _match_host
+        order = self._order_batch(b["scores"], b["img"], cls, C + 2)
+        scores, cls, boxes = b["scores"][order].contiguous(), cls[order].contiguous(), b["boxes"][order].contiguous()
+        match = K.voc_match if self._device.type == "cuda" else _match_host
         ss, cs = (_SCORE_SCALE, _COORD_SCALE) if self.file_roundtrip else (0.0, 0.0)
-        flags, qscores = match(boxes, scores, cls, det_off, gboxes, glabels, gdiff, gt_off, max(nd), max(ng), self.ovthresh, ss, cs,
-                               self._counters[0], self._counters[1], self._counters[2])
-        self._append({"score": qscores, "flag": flags, "cls": torch.where(cls == 0, C + 1, cls) - 1, "img": ids[img], "ord": pos})
-
-    def merge(self, group=None):
-        """Gather the records of every rank and all-reduce the counters: afterwards every rank summarizes the whole run.  A no-op
-        without an initialised process group."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return
-        if self._merged:
-            raise RuntimeError("VOCDetectionMeter: merge() called twice; reset() first")
-        C = self.num_classes
-        dev = self._device if self._device is not None else torch.device("cuda" if dist.get_backend(group) == "nccl" else "cpu")
-        if self._counters is None:                                              # a rank that saw no image
-            self._device, self._counters = dev, torch.zeros((3, C), dtype=torch.int32, device=dev)
-        world = dist.get_world_size(group)
-
-        gather = lambda t: _all_gather_rows(t, world, group)
-        dtypes = {"score": torch.float64, "flag": torch.uint8, "cls": torch.int64, "img": torch.int64, "ord": torch.int32}
-        cols = {k: gather(self._cols[k][:self._n] if self._cols is not None else torch.empty((0,), dtype=dt, device=dev))
-                for k, dt in dtypes.items()}
-        self._ids = [gather(torch.cat(self._ids) if self._ids else torch.empty((0,), dtype=torch.int64, device=dev))]
-        self._cols, self._n = cols, cols["flag"].numel()
-        dist.all_reduce(self._counters, group=group)
-        self._merged = True
+        flags, qscores = match(boxes, scores, cls, b["det_off"], b["gboxes"], b["glabels"], b["difficult"], b["gt_off"], b["max_det"],
+                               b["max_gt"], self.ovthresh, ss, cs, self._counters[0], self._counters[1], self._counters[2])
+        self._append({"score": qscores, "flag": flags, "cls": torch.where(cls == 0, C + 1, cls) - 1, "img": b["ids"][b["img"]],
+                      "ord": b["pos"]})
 
     @torch.no_grad()
     def summarize(self, use_07_metric=True, return_curves=False):
@@ -245,26 +295,12 @@ class VOCDetectionMeter:
         but no non-difficult ground truth has area AP NaN, as in the reference, and the means propagate them (np.mean).
         return_curves adds 'rec', 'prec', 'flags': per class, in curve order."""
         C = self.num_classes
-        if self._counters is None:
-            raise RuntimeError("VOCDetectionMeter.summarize: nothing accumulated")
-        ids = torch.sort(torch.cat(self._ids)).values
-        if bool((ids[1:] == ids[:-1]).any()):
-            raise ValueError("VOCDetectionMeter: an image id was accumulated twice")
-        dev, n = self._device, self._n
-        if self._cols is None:
-            self._append({"score": torch.empty(0, dtype=torch.float64, device=dev), "flag": torch.empty(0, dtype=torch.uint8, device=dev),
-                          "cls": torch.empty(0, dtype=torch.int64, device=dev), "img": torch.empty(0, dtype=torch.int64, device=dev),
-                          "ord": torch.empty(0, dtype=torch.int32, device=dev)})
-        col = {k: v[:n] for k, v in self._cols.items()}
-        # curve order by stable sorts, last key first: class, score descending, image id, position inside the image
-        o = torch.sort(col["ord"], stable=True).indices
-        o = o[torch.sort(col["img"][o], stable=True).indices]
-        o = o[torch.sort(col["score"][o], descending=True, stable=True).indices]
-        o = o[torch.sort(col["cls"][o], stable=True).indices]
-        flags, cls = col["flag"][o].contiguous(), col["cls"][o].contiguous()
-        seg_off = torch.searchsorted(cls, torch.arange(C + 1, device=dev)).to(torch.int32)       # dropped labels (class C) lie behind
+        self._check_run()
+        # class, score descending, image id, position inside the image; dropped labels (class C) lie behind
+        col, seg_off = self._curve_order(("ord", "img", "score", "cls"), C, ("flag", "cls"))
+        flags = col["flag"]
         npos = self._counters[0].contiguous()
-        ap = K.voc_ap if dev.type == "cuda" else _ap_host
+        ap = K.voc_ap if self._device.type == "cuda" else _ap_host
         ap07, area, rec, prec = ap(flags, seg_off, npos, return_curves)
         cnt = self._counters.cpu().numpy()
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -381,7 +417,7 @@ def _coco_accumulate_host(words, rank, scores, seg_off, npig, max_dets, rec_thrs
     return t(precision), t(recall), t(score_at)
 
 
-class COCODetectionMeter:
+class COCODetectionMeter(_DetectionMeter):
     """Accumulates the COCO detection metrics over an evaluation run: the twelve numbers of COCOeval.summarize() for 'bbox' and the
     precision / recall / scores tables behind them (what the reference's CocoEvaluator returns as coco_eval['bbox'].stats / .eval).
 
@@ -406,21 +442,15 @@ class COCODetectionMeter:
         self.params = coco_params()
         self.reset()
 
-    def reset(self):
-        self._device = None
-        self._n, self._cols = 0, None          # records: capacity-sized tensors, the first _n rows valid
-        self._ids = []                         # image ids of every update (images without detections included)
-        self._npig = None                      # int32 [K, 4]
-        self._dev_params = None
-        self._merged = False
-
-    _append = _append_rows
+    _SCHEMA = {"score": (torch.float32, ()), "words": (torch.int32, (K.COCO_A,)), "rank": (torch.int32, ()), "cat": (torch.int64, ()),
+               "img": (torch.int64, ())}
+    _MAX_GT = K.COCO_MAX_GT
 
     def _start(self, dev):
-        """First use of a device: the counter and the parameter arrays (numpy's values) in one copy."""
+        """First use of a device: the counter npig and the parameter arrays (numpy's values) in one copy."""
         P, Kc = self.params, len(self.cat_ids)
         self._device = dev
-        self._npig = torch.zeros((Kc, K.COCO_A), dtype=torch.int32, device=dev)
+        self._counters = torch.zeros((Kc, K.COCO_A), dtype=torch.int32, device=dev)
         f = torch.from_numpy(np.concatenate([P["iouThrs"], np.asarray(P["areaRng"], np.float64).reshape(-1), P["recThrs"]]))
         i = torch.tensor(self.cat_ids + list(P["maxDets"]), dtype=torch.int64)
         if dev.type == "cuda":
@@ -429,83 +459,25 @@ class COCODetectionMeter:
         self._dev_params = {"iouThrs": f[:T], "areaRng": f[T:T + 2 * A], "recThrs": f[T + 2 * A:], "cat_ids": i[:Kc],
                             "maxDets": i[Kc:].to(torch.int32)}
 
-    def _empty_cols(self, dev):
-        return {"score": torch.empty(0, dtype=torch.float32, device=dev), "words": torch.empty((0, K.COCO_A), dtype=torch.int32, device=dev),
-                "rank": torch.empty(0, dtype=torch.int32, device=dev), "cat": torch.empty(0, dtype=torch.int64, device=dev),
-                "img": torch.empty(0, dtype=torch.int64, device=dev)}
-
     @torch.no_grad()
     def update(self, results, gts):
-        if self._merged:
-            raise RuntimeError("COCODetectionMeter: update() after merge(); reset() first")
-        if len(results) != len(gts):
-            raise ValueError("COCODetectionMeter.update: one ground-truth dict per result")
-        if not results:
+        b = self._collect(results, gts, {"iscrowd": torch.uint8, "area": torch.float64})
+        if b is None:
             return
-        dev, Kc = results[0]["scores"].device, len(self.cat_ids)
-        if self._device is None:
-            self._start(dev)
-        elif dev != self._device:
-            raise ValueError(f"COCODetectionMeter: tensors on {dev}, earlier updates on {self._device}")
-        nd = [int(r["scores"].shape[0]) for r in results]                       # host lengths: the shapes we are handed
-        ng = [int(g["labels"].shape[0]) for g in gts]
-        if max(nd) > K.COCO_MAX_DET or max(ng) > K.COCO_MAX_GT:
-            raise ValueError(f"at most {K.COCO_MAX_DET} detections and {K.COCO_MAX_GT} ground-truth boxes per image")
-        scores = torch.cat([r["scores"].reshape(-1) for r in results]).float()
-        labels = torch.cat([r["labels"].reshape(-1) for r in results]).long()
-        boxes = torch.cat([r["boxes"].reshape(-1, 4) for r in results]).float()
-        gboxes = torch.cat([g["boxes"].reshape(-1, 4) for g in gts]).to(dev, torch.float64).contiguous()
-        glabels = torch.cat([g["labels"].reshape(-1) for g in gts]).to(dev, torch.int64)
-        gcrowd = torch.cat([g["iscrowd"].reshape(-1) for g in gts]).to(dev).ne(0).to(torch.uint8)
-        garea = torch.cat([g["area"].reshape(-1) for g in gts]).to(dev, torch.float64).contiguous()
-        # offsets, the image of every row and the image ids: what the host knows from the shapes goes up in ONE copy
-        ids = [g["image_id"] for g in gts]
-        ids_dev = None
-        if any(torch.is_tensor(i) for i in ids):
-            ids_dev, ids = torch.stack([torch.as_tensor(i).reshape(()).to(dev, torch.int64) for i in ids]), []
-        nimg, ndt = len(nd), sum(nd)
-        host = torch.from_numpy(np.concatenate([[0], np.cumsum(nd), [0], np.cumsum(ng), np.repeat(np.arange(nimg), nd), ids]).astype(np.int64))
-        if dev.type == "cuda":
-            host = host.pin_memory().to(dev, non_blocking=True)
-        det_off, gt_off = host[:nimg + 1].to(torch.int32), host[nimg + 1:2 * nimg + 2].to(torch.int32)
-        img = host[2 * nimg + 2:2 * nimg + 2 + ndt]
-        ids = ids_dev if ids_dev is not None else host[2 * nimg + 2 + ndt:]
-        self._ids.append(ids)
         # category id -> index into cat_ids; ids that are not in the list become Kc and gather at the end of the image
-        cid = self._dev_params["cat_ids"]
+        Kc, cid = len(self.cat_ids), self._dev_params["cat_ids"]
 
         def index_of(lab):
             at = torch.searchsorted(cid, lab).clamp(max=Kc - 1)
             return torch.where(cid[at] == lab, at, Kc)
-        cat, gcat = index_of(labels), index_of(glabels)
-        # (category ascending, score descending) inside every image, equal scores in incoming order
-        o1 = torch.sort(scores, descending=True, stable=True).indices
-        o2 = torch.sort(img[o1] * (Kc + 1) + cat[o1], stable=True).indices
-        order = o1[o2]
-        scores, cat, boxes = scores[order].contiguous(), cat[order].contiguous(), boxes[order].contiguous()
-        match = K.coco_match if dev.type == "cuda" else _coco_match_host
-        rank, words = match(boxes, cat, det_off, gboxes, gcat, gcrowd, garea, gt_off, self._dev_params["iouThrs"],
-                            self._dev_params["areaRng"], max(nd), max(ng), self.params["maxDets"][-1], self._npig)
+        cat, gcat = index_of(b["labels"]), index_of(b["glabels"])
+        order = self._order_batch(b["scores"], b["img"], cat, Kc + 1)
+        scores, cat, boxes = b["scores"][order].contiguous(), cat[order].contiguous(), b["boxes"][order].contiguous()
+        match = K.coco_match if self._device.type == "cuda" else _coco_match_host
+        rank, words = match(boxes, cat, b["det_off"], b["gboxes"], gcat, b["iscrowd"], b["area"], b["gt_off"], self._dev_params["iouThrs"],
+                            self._dev_params["areaRng"], b["max_det"], b["max_gt"], self.params["maxDets"][-1], self._counters)
         # a detection that was not evaluated (no category, or past the first 100) moves behind every category
-        self._append({"score": scores, "words": words, "rank": rank, "cat": torch.where(rank < 0, Kc, cat), "img": ids[img]})
-
-    def merge(self, group=None):
-        """Gather the records of every rank and all-reduce npig: afterwards every rank summarizes the whole run.  A no-op without an
-        initialised process group."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return
-        if self._merged:
-            raise RuntimeError("COCODetectionMeter: merge() called twice; reset() first")
-        if self._device is None:                                                # a rank that saw no image
-            self._start(torch.device("cuda" if dist.get_backend(group) == "nccl" else "cpu"))
-        dev, world = self._device, dist.get_world_size(group)
-        mine = {k: v[:self._n] for k, v in self._cols.items()} if self._cols is not None else self._empty_cols(dev)
-        cols = {k: _all_gather_rows(mine[k], world, group) for k in ("score", "words", "rank", "cat", "img")}
-        self._ids = [_all_gather_rows(torch.cat(self._ids) if self._ids else torch.empty((0,), dtype=torch.int64, device=dev), world, group)]
-        self._cols, self._n = cols, cols["rank"].shape[0]
-        dist.all_reduce(self._npig, group=group)
-        self._merged = True
+        self._append({"score": scores, "words": words, "rank": rank, "cat": torch.where(rank < 0, Kc, cat), "img": b["ids"][b["img"]]})
 
     @torch.no_grad()
     def summarize(self, return_records=False):
@@ -514,22 +486,12 @@ class COCODetectionMeter:
         [T,K,A,M], 'scores' [T,R,K,A,M]} as COCOeval.eval holds them (-1: no ground truth to find), 'npig' int32 [K,4]} - numpy arrays.
         return_records adds 'records': 'cat' (index into cat_ids), 'img', 'rank', 'score', 'words' [n,4] of the evaluated detections, per
         category in curve order."""
-        if self._npig is None:
-            raise RuntimeError("COCODetectionMeter.summarize: nothing accumulated")
-        ids = torch.sort(torch.cat(self._ids)).values
-        if bool((ids[1:] == ids[:-1]).any()):
-            raise ValueError("COCODetectionMeter: an image id was accumulated twice")
-        dev, n, Kc, P = self._device, self._n, len(self.cat_ids), self.params
-        col = {k: v[:n] for k, v in self._cols.items()} if self._cols is not None else self._empty_cols(dev)
-        # curve order by stable sorts, last key first: category, score descending, image id, rank
-        o = torch.sort(col["rank"], stable=True).indices
-        o = o[torch.sort(col["img"][o], stable=True).indices]
-        o = o[torch.sort(col["score"][o], descending=True, stable=True).indices]
-        o = o[torch.sort(col["cat"][o], stable=True).indices]
-        col = {k: v[o].contiguous() for k, v in col.items()}
-        seg_off = torch.searchsorted(col["cat"], torch.arange(Kc + 1, device=dev)).to(torch.int32)     # category Kc: not evaluated, behind
-        acc = K.coco_accumulate if dev.type == "cuda" else _coco_accumulate_host
-        precision, recall, scores = acc(col["words"], col["rank"], col["score"], seg_off, self._npig.contiguous(),
+        self._check_run()
+        Kc, P = len(self.cat_ids), self.params
+        # category, score descending, image id, rank; category Kc (not evaluated) lies behind
+        col, seg_off = self._curve_order(("rank", "img", "score", "cat"), Kc, tuple(self._SCHEMA))
+        acc = K.coco_accumulate if self._device.type == "cuda" else _coco_accumulate_host
+        precision, recall, scores = acc(col["words"], col["rank"], col["score"], seg_off, self._counters.contiguous(),
                                         self._dev_params["maxDets"], self._dev_params["recThrs"])
         precision, recall, scores = precision.cpu().numpy(), recall.cpu().numpy(), scores.cpu().numpy()
 
@@ -544,7 +506,7 @@ class COCODetectionMeter:
                           one(1, area="medium", max_dets=d100), one(1, area="large", max_dets=d100), one(0, max_dets=d1),
                           one(0, max_dets=d10), one(0, max_dets=d100), one(0, area="small", max_dets=d100),
                           one(0, area="medium", max_dets=d100), one(0, area="large", max_dets=d100)], np.float64)
-        out = {"stats": stats, "npig": self._npig.cpu().numpy().copy(),
+        out = {"stats": stats, "npig": self._counters.cpu().numpy().copy(),
                "eval": {"params": {**P, "catIds": list(self.cat_ids)}, "counts": [K.COCO_T, len(P["recThrs"]), Kc, K.COCO_A, len(P["maxDets"])],
                         "precision": precision, "recall": recall, "scores": scores}}
         if return_records:

@@ -1737,9 +1737,21 @@ def pos_learned_bwd(g, B, h, w, npf, need_col=True, need_row=True, dcol_out=None
     return outs[0], outs[1]
 
 
+# ---- detection metrics: what the two meters share (csrc/det_eval_common.h) ------------------------
+MAX_DET = 4096             # detections per image spe_voc_match and spe_coco_match take (-2 beyond)
+VOC_MAX_DET = COCO_MAX_DET = MAX_DET
+
+
+def _check_typed(name, pairs):
+    for t, dt in pairs:
+        if not t.is_cuda:
+            raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+        if t.dtype != dt or not t.is_contiguous():
+            raise TypeError(f"{name}: expected a contiguous {dt} tensor, got {t.dtype}")
+
+
 # ---- PASCAL VOC detection metrics (csrc/voc_eval.hip) ---------------------------------------------
-VOC_MAX_DET = 4096         # detections / ground-truth boxes per image spe_voc_match takes (-2 beyond)
-VOC_MAX_GT = 1024
+VOC_MAX_GT = 1024          # ground-truth boxes per image spe_voc_match takes (-2 beyond)
 
 
 def voc_match(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_difficult, gt_off, max_det, max_gt,
@@ -1748,13 +1760,9 @@ def voc_match(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, g
     [ng] uint8, both concatenated over the images with int32 offsets [nimg+1]; detections ordered by (label asc, score desc) inside
     an image.  max_det / max_gt: the largest per-image counts (host ints).  Adds into the int32 counters npos / nimgs / hits [C].
     -> (flags uint8 [nd]: 0 ignored, 1 tp, 2 fp; scores fp64 [nd], quantised when score_scale != 0)."""
-    for t, dt in ((det_boxes, torch.float32), (det_scores, torch.float32), (det_labels, torch.int64), (det_off, torch.int32),
-                  (gt_boxes, torch.float64), (gt_labels, torch.int64), (gt_difficult, torch.uint8), (gt_off, torch.int32),
-                  (npos, torch.int32), (nimgs, torch.int32), (hits, torch.int32)):
-        if not t.is_cuda:
-            raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
-        if t.dtype != dt or not t.is_contiguous():
-            raise TypeError(f"voc_match: expected a contiguous {dt} tensor, got {t.dtype}")
+    _check_typed("voc_match", ((det_boxes, torch.float32), (det_scores, torch.float32), (det_labels, torch.int64), (det_off, torch.int32),
+                               (gt_boxes, torch.float64), (gt_labels, torch.int64), (gt_difficult, torch.uint8), (gt_off, torch.int32),
+                               (npos, torch.int32), (nimgs, torch.int32), (hits, torch.int32)))
     nd, C, nimg = det_scores.numel(), npos.numel(), det_off.numel() - 1
     if gt_off.numel() != nimg + 1 or nimgs.numel() != C or hits.numel() != C or det_boxes.numel() != nd * 4 or \
             det_labels.numel() != nd or gt_boxes.numel() != gt_labels.numel() * 4 or gt_difficult.numel() != gt_labels.numel():
@@ -1770,11 +1778,7 @@ def voc_match(det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, g
 def voc_ap(flags, seg_off, npos, want_curve=False):
     """flags uint8 [nd] sorted per class (class c = seg_off[c] .. seg_off[c+1], int32 [C+1]) in curve order, npos int32 [C]
     -> (ap07 [C], ap_area [C], rec [nd] or None, prec [nd] or None), fp64 on the device."""
-    for t, dt in ((flags, torch.uint8), (seg_off, torch.int32), (npos, torch.int32)):
-        if not t.is_cuda:
-            raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
-        if t.dtype != dt or not t.is_contiguous():
-            raise TypeError(f"voc_ap: expected a contiguous {dt} tensor, got {t.dtype}")
+    _check_typed("voc_ap", ((flags, torch.uint8), (seg_off, torch.int32), (npos, torch.int32)))
     C = npos.numel()
     if seg_off.numel() != C + 1:
         raise ValueError("voc_ap: seg_off must hold num_classes + 1 offsets")
@@ -1786,18 +1790,9 @@ def voc_ap(flags, seg_off, npos, want_curve=False):
 
 
 # ---- COCO detection metrics (csrc/coco_eval.hip) ---------------------------------------------------
-COCO_MAX_DET = 4096        # detections / ground-truth boxes per image spe_coco_match takes (-2 beyond)
-COCO_MAX_GT = 512
+COCO_MAX_GT = 512          # ground-truth boxes per image spe_coco_match takes (-2 beyond)
 COCO_T, COCO_A = 10, 4     # IoU thresholds and area ranges a flag word is laid out for
 COCO_MAX_REC = 128         # recall thresholds spe_coco_accumulate takes (-2 beyond)
-
-
-def _coco_check(name, pairs):
-    for t, dt in pairs:
-        if not t.is_cuda:
-            raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
-        if t.dtype != dt or not t.is_contiguous():
-            raise TypeError(f"{name}: expected a contiguous {dt} tensor, got {t.dtype}")
 
 
 def coco_match(det_boxes, det_cats, det_off, gt_boxes, gt_cats, gt_iscrowd, gt_area, gt_off, iou_thrs, area_rng, max_det, max_gt,
@@ -1808,9 +1803,9 @@ def coco_match(det_boxes, det_cats, det_off, gt_boxes, gt_cats, gt_iscrowd, gt_a
     on the device.  max_det / max_gt: the largest per-image counts (host ints); top: maxDets' last entry.  Adds into npig int32 [K,4].
     -> (rank int32 [nd]: position inside the (image, category), -1 not evaluated; words int32 [nd,4]: per area range the matched bits of
     the 10 thresholds in bits 0 .. 9 and the ignore bits in bits 10 .. 19)."""
-    _coco_check("coco_match", ((det_boxes, torch.float32), (det_cats, torch.int64), (det_off, torch.int32), (gt_boxes, torch.float64),
-                               (gt_cats, torch.int64), (gt_iscrowd, torch.uint8), (gt_area, torch.float64), (gt_off, torch.int32),
-                               (iou_thrs, torch.float64), (area_rng, torch.float64), (npig, torch.int32)))
+    _check_typed("coco_match", ((det_boxes, torch.float32), (det_cats, torch.int64), (det_off, torch.int32), (gt_boxes, torch.float64),
+                                (gt_cats, torch.int64), (gt_iscrowd, torch.uint8), (gt_area, torch.float64), (gt_off, torch.int32),
+                                (iou_thrs, torch.float64), (area_rng, torch.float64), (npig, torch.int32)))
     nd, ng, nimg = det_cats.numel(), gt_cats.numel(), det_off.numel() - 1
     if gt_off.numel() != nimg + 1 or det_boxes.numel() != nd * 4 or gt_boxes.numel() != ng * 4 or gt_iscrowd.numel() != ng or \
             gt_area.numel() != ng or iou_thrs.numel() != COCO_T or area_rng.numel() != 2 * COCO_A or npig.dim() != 2 or \
@@ -1827,8 +1822,8 @@ def coco_accumulate(words, rank, scores, seg_off, npig, max_dets, rec_thrs):
     """Records sorted per category (category k = seg_off[k] .. seg_off[k+1], int32 [K+1]) in curve order: words int32 [n,4], rank int32
     [n], scores fp32 [n]; npig int32 [K,4], max_dets int32 [M], rec_thrs fp64 [R] ascending
     -> (precision [10,R,K,4,M], recall [10,K,4,M], scores [10,R,K,4,M]), fp64 on the device, COCOeval's layouts, -1 where npig = 0."""
-    _coco_check("coco_accumulate", ((words, torch.int32), (rank, torch.int32), (scores, torch.float32), (seg_off, torch.int32),
-                                    (npig, torch.int32), (max_dets, torch.int32), (rec_thrs, torch.float64)))
+    _check_typed("coco_accumulate", ((words, torch.int32), (rank, torch.int32), (scores, torch.float32), (seg_off, torch.int32),
+                                     (npig, torch.int32), (max_dets, torch.int32), (rec_thrs, torch.float64)))
     n, Kc, M, R = rank.numel(), npig.shape[0], max_dets.numel(), rec_thrs.numel()
     if words.numel() != n * COCO_A or scores.numel() != n or seg_off.numel() != Kc + 1 or npig.dim() != 2 or npig.shape[1] != COCO_A:
         raise ValueError("coco_accumulate: inconsistent shapes")

@@ -210,7 +210,7 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, out):
+def _worker(rank, world, port, out, idle_rank=None):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     ok, sizes = True, []
@@ -218,6 +218,8 @@ def _worker(rank, world, port, out):
         cat_ids, images = cases.case(name)
         single = run_meter(images, cat_ids).summarize(return_records=True)
         mine = [i for i in range(len(images)) if (i * 7 + 3) % 5 % world == rank]      # an uneven split; a rank may see no image
+        if idle_rank is not None:                                                      # every image to rank 0, none to the idle rank
+            mine = [] if rank == idle_rank else list(range(len(images)))
         m = run_meter(images, cat_ids, [b for b in (mine[:1], mine[1:]) if b])
         m.merge()
         got = m.summarize(return_records=True)
@@ -243,6 +245,16 @@ def test_gloo_world2_merge():
     res = dict(out)
     assert res[0][0] and res[1][0], res
     assert [a + b for a, b in zip(res[0][1], res[1][1])] == [len(cases.case(n)[1]) for n in cases.CASES]
+
+
+def test_gloo_world2_merge_with_a_rank_that_saw_no_image():
+    world = 2
+    port = _free_port()
+    out = mp.Manager().dict()
+    mp.spawn(_worker, args=(world, port, out, 1), nprocs=world, join=True)      # rank 1 makes no update() call at all, in any case
+    res = dict(out)
+    assert res[0][0] and res[1][0], res
+    assert res[0][1] == [len(cases.case(n)[1]) for n in cases.CASES] and not any(res[1][1])
 
 
 def test_merge_without_process_group_is_a_noop():

@@ -135,14 +135,16 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, out):
+def _worker(rank, world, port, out, idle_rank=None):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     g = load_golden("voc_eval_small")
     C, images = g["num_classes"], g["images"]
     single = run_meter(images, C).summarize(return_curves=True)
     mine = [i for i in range(len(images)) if (i * 7 + 3) % 5 % world == rank]      # an uneven split
-    m = run_meter(images, C, [mine[:5], mine[5:]])
+    if idle_rank is not None:                                                      # every image to rank 0, none to the idle rank
+        mine = [] if rank == idle_rank else list(range(len(images)))
+    m = run_meter(images, C, [b for b in (mine[:5], mine[5:]) if b])
     m.merge()
     got = m.summarize(return_curves=True)
     ok = all(same(got[k], single[k]) for k in ("ap07", "ap_area", "corloc", "npos", "nimgs", "map", "mean_corloc"))
@@ -165,6 +167,14 @@ def test_gloo_world2_merge():
     res = dict(out)
     assert res[0][0] and res[1][0], res
     assert res[0][1] + res[1][1] == 40 and res[0][1] != res[1][1]
+
+
+def test_gloo_world2_merge_with_a_rank_that_saw_no_image():
+    world = 2
+    port = _free_port()
+    out = mp.Manager().dict()
+    mp.spawn(_worker, args=(world, port, out, 1), nprocs=world, join=True)      # rank 1 makes no update() call at all
+    assert dict(out) == {0: (True, 40), 1: (True, 0)}
 
 
 def test_merge_without_process_group_is_a_noop():
