@@ -39,8 +39,9 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_gemm_bf16nt_plan / spe_gemm_bf16tn_plan (the kernel selection of the 16-bit NT GEMM family / of the TN weight-gradient GEMM, host only),
  * spe_pos_learned_fwd / _bwd (the learned position embedding), spe_cam_boxes_device(_workspace) (the CAM pseudo boxes found on the device), spe_voc_match / spe_voc_ap (VOC AP and CorLoc on the device),
  * spe_coco_match / spe_coco_accumulate (the COCO AP / AR tables on the device),
- * spe_resample_plan / _tables / _h / _v (the input transforms: Pillow-exact bilinear resize, crop, flip, normalise, pad)
- * - 95 entry points */
+ * spe_resample_plan / _tables / _h / _v (the input transforms: Pillow-exact bilinear resize, crop, flip, normalise, pad),
+ * spe_ledger_state_bytes / _record / _total_bwd / _summary (the step ledger: weighted total, loss meters and non-finite guard on the device)
+ * - 99 entry points */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -670,6 +671,39 @@ int spe_resample_tables(const long* desc_host, const long* desc_dev, int n, int*
 int spe_resample_h(const long* desc_host, const long* desc_dev, int n, const int* tables, unsigned char* tmp, spe_stream_t stream);
 int spe_resample_v(const long* desc_host, const long* desc_dev, int n, const int* tables, const unsigned char* tmp, const float* lut,
                    float* out, unsigned char* mask, int Hmax, int Wmax, spe_stream_t stream);
+
+/* ---- step ledger: the loss bookkeeping of a training step (reference engine.py:134-169, util/misc.py:34-93, 139-253;
+ * csrc/step_ledger.hip, compiled without FMA contraction).  K loss values per step (1 <= K <= 256), E host scalars such as lr
+ * (0 <= E <= 8), a ring of D = 64 steps, so a meter window is 1 .. 64.  Meters, in this order: K unscaled values, K scaled values
+ * v * w (a key outside the mask keeps its slot, which is no meter of the reference and is never added to), `loss`, E extras:
+ * M = 2K + 1 + E.  Single-workgroup launches, one thread (record) or one wave (summary) per meter, no atomics: bitwise reproducible.
+ * state: caller-owned device memory, 8-B aligned, of at least the bytes spe_ledger_state_bytes reports (host function; bytes: host
+ *   pointer); all-zero bytes are an empty ledger.  Layout: long steps, long first bad step + 1 (0: none), 2 longs reserved;
+ *   double totals [M]; double extras ring [D][E]; float value ring [D][K]; float weight ring [D][K]; the newest mask [K], padded to 8.
+ * spe_ledger_record: vals / weights [K] fp32, mask [K] bytes (non-zero: the key is in the weight dict; expected to stay the same
+ *   through a run), extras_host [E] doubles in HOST memory (passed on by value).  scaled_k = v_k * w_k in fp32;
+ *   total = ((0.0f + s_a) + s_b) + ... over the masked keys in index order by one lane - Python's sum() over fp32 tensors bit for
+ *   bit - written to total [1]; v, w and the extras go to ring row step % D; (double)v_k, (double)scaled_k of masked keys,
+ *   (double)total and the extras are added to the totals; steps += 1; a non-finite total records its step unless one is recorded
+ *   already (sticky).  A non-finite value under an unmasked key records nothing; 0 * NaN under a masked key does.
+ * spe_ledger_total_bwd: dvals[k] = mask[k] ? weights[k] * g[0] : 0 (g: the 0-dim upstream gradient).
+ * spe_ledger_summary: out [M * 5 + 2] fp64: [M][5] = median, avg, global_avg, max, value of every meter over its last
+ *   n = min(steps, window) steps, then steps and first bad step + 1 as doubles (one copy tells the host everything).  windows: [M] int32, the same table in host memory (validated) and in device memory (read by the kernel).
+ *   ring_override: NULL, or a [D][K] fp32 ring that replaces the state's value ring (the rank-averaged one); weights, extras and
+ *   totals always come from the state.  order: NULL, or [K] int32 - the key order in which `loss` is re-summed (the reference sums
+ *   it in sorted key order once reduce_dict has rebuilt the dict).  Scaled values and `loss` are recomputed from the ring rows with
+ *   the two expressions above.  median = float32 sorted[(n - 1) / 2] (ranks by counting, ties by position: torch.median's lower
+ *   median), avg = float32(fp64 in-order sum / n), max = the largest, value = the newest, global_avg = totals / steps.  A NaN in
+ *   the window makes median and max NaN.  steps = 0: every field NaN.
+ * Status, before any launch: -2 K or E out of range, a window outside 1 .. 64, a NULL pointer other than the state, ring_override
+ *   and order (extras_host may be NULL when E = 0); -4 state NULL, misaligned or smaller
+ *   than spe_ledger_state_bytes.  A refused call writes nothing. */
+int spe_ledger_state_bytes(int K, int E, size_t* bytes);
+int spe_ledger_record(const float* vals, const float* weights, const unsigned char* mask, const double* extras_host, int K, int E,
+                      void* state, size_t state_bytes, float* total, spe_stream_t stream);
+int spe_ledger_total_bwd(const float* g, const float* weights, const unsigned char* mask, int K, float* dvals, spe_stream_t stream);
+int spe_ledger_summary(void* state, size_t state_bytes, int K, int E, const int* windows_host, const int* windows_dev,
+                       const float* ring_override, const int* order, double* out, spe_stream_t stream);
 
 /* ---- optimiser step on flat buffers (reference engine.py:161-165: clip_grad_norm_(params, 0.1) + AdamW.step(),
  * parameter groups of main.py:177-191).  spe_sqnorm_partials: partials[b] = sum g^2 over the b-th of nblocks chunks.

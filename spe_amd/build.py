@@ -24,7 +24,9 @@ EXTRA_FLAGS = {"attn_flash_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # coco_eval.hip restates COCOeval's fp64 IoU the same way: iou == threshold must match, equal IoUs must stay equal
                "coco_eval.hip": ["-ffp-contract=off"],
                # img_resample.hip restates Pillow's fp64 coefficient arithmetic in a fixed operation order
-               "img_resample.hip": ["-ffp-contract=off"]}
+               "img_resample.hip": ["-ffp-contract=off"],
+               # step_ledger.hip restates Python's sum() over fp32 loss tensors: each product v * w is rounded before it is added, never fused
+               "step_ledger.hip": ["-ffp-contract=off"]}
 
 
 def flags_for(src):

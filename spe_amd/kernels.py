@@ -1835,6 +1835,55 @@ def coco_accumulate(words, rank, scores, seg_off, npig, max_dets, rec_thrs):
     return prec, rec, sco
 
 
+# ---- step ledger: weighted total, loss meters and non-finite guard of a training step (csrc/step_ledger.hip) ----------------------
+LEDGER_MAX_K, LEDGER_MAX_E, LEDGER_D = 256, 8, 64      # loss values per step, host scalars per step, ring rows (= the largest window)
+
+
+def ledger_state_bytes(K, E):
+    """Bytes of the caller-owned state block of a ledger with K loss values and E host scalars per step (host only)."""
+    n = ctypes.c_size_t(0)
+    _call("spe_ledger_state_bytes", int(K), int(E), ctypes.addressof(n))
+    return int(n.value)
+
+
+def ledger_record(vals, weights, mask, extras, state):
+    """One step: vals / weights fp32 [K], mask uint8 [K], extras a sequence of E host floats, state the uint8 block of
+    ledger_state_bytes(K, E) (zeroed = empty).  -> the 0-dim fp32 weighted total; everything else lands in the state."""
+    _check_typed("ledger_record", ((vals, torch.float32), (weights, torch.float32), (mask, torch.uint8), (state, torch.uint8)))
+    Kk, E = vals.numel(), len(extras)
+    if weights.numel() != Kk or mask.numel() != Kk:
+        raise ValueError("ledger_record: vals, weights and mask must have one length")
+    ex = (ctypes.c_double * max(E, 1))(*[float(e) for e in extras])
+    total = torch.empty((), device=vals.device, dtype=torch.float32)
+    _call("spe_ledger_record", _p(vals), _p(weights), _p(mask), ctypes.addressof(ex), Kk, E, _p(state), state.numel(), _p(total), _st())
+    return total
+
+
+def ledger_total_bwd(g, weights, mask):
+    """d total / d vals = mask ? weights * g : 0 for the 0-dim upstream gradient g."""
+    _check_typed("ledger_total_bwd", ((g, torch.float32), (weights, torch.float32), (mask, torch.uint8)))
+    out = torch.empty_like(weights)
+    _call("spe_ledger_total_bwd", _p(g), _p(weights), _p(mask), weights.numel(), _p(out), _st())
+    return out
+
+
+def ledger_summary(state, K_, E, windows_host, windows_dev, ring=None, order=None):
+    """-> fp64 [M * 5 + 2] on the device, M = 2 K + 1 + E: per meter median, avg, global_avg, max, value; then steps and first bad
+    step + 1.  windows_host: int32 CPU tensor [M] (validated), windows_dev its device copy; ring: fp32 [64, K] replacing the state's
+    value ring; order: int32 [K] summation order of `loss`."""
+    _check_typed("ledger_summary", [(state, torch.uint8), (windows_dev, torch.int32)] + ([(ring, torch.float32)] if ring is not None else []) +
+                 ([(order, torch.int32)] if order is not None else []))
+    M = 2 * K_ + 1 + E
+    if windows_host.is_cuda or windows_host.dtype != torch.int32 or windows_host.numel() != M or windows_dev.numel() != M:
+        raise ValueError("ledger_summary: windows must be int32 [2 K + 1 + E], once on the host and once on the device")
+    if (ring is not None and ring.numel() != LEDGER_D * K_) or (order is not None and order.numel() != K_):
+        raise ValueError("ledger_summary: ring must be [64, K] and order [K]")
+    out = torch.empty((M * 5 + 2,), device=state.device, dtype=torch.float64)
+    _call("spe_ledger_summary", _p(state), state.numel(), int(K_), int(E), windows_host.data_ptr(), _p(windows_dev), _p(ring), _p(order),
+          _p(out), _st())
+    return out
+
+
 # ---- input transforms: Pillow-exact bilinear resize, crop, flip, normalise, pad (csrc/img_resample.hip) ----------------------------
 RESAMPLE_MAX_TAPS = 65     # taps per output element spe_resample_* take (-5 beyond): a 32x downscale
 RESAMPLE_DESC = 16         # longs per image descriptor (include/spe_hip.h)

@@ -1280,3 +1280,30 @@ class _PosLearned(Function):
 def pos_learned(col, row, B, h, w):
     """[B,h,w,2*npf] learned position features of an h x w grid (h, w <= 50), the same for every image of the batch."""
     return _PosLearned.apply(col, row, int(B), int(h), int(w))
+
+
+class _LedgerTotal(Function):
+    """The step ledger's record launch as an autograd node (reference engine.py:144: losses = sum(loss_dict[k] * weight_dict[k] ...);
+    csrc/step_ledger.hip): forward files the [K] stacked loss values in the ledger's state and returns the weighted total, backward
+    is one launch, d total / d vals_k = w_k for the keys of the weight dict and 0 for the others.  CPU tensors take the host
+    restatement of spe_amd.steplog with the same arithmetic."""
+
+    @staticmethod
+    def forward(ctx, vals, weights, mask, extras, state):
+        ctx.save_for_backward(weights, mask)
+        if vals.is_cuda:
+            return K.ledger_record(vals, weights, mask, extras, state)
+        from . import steplog
+        return steplog.record_host(vals, weights, mask, extras, state)
+
+    @staticmethod
+    def backward(ctx, g):
+        weights, mask = ctx.saved_tensors
+        if g.is_cuda:
+            return K.ledger_total_bwd(g.contiguous(), weights, mask), None, None, None, None
+        return torch.where(mask != 0, weights * g, torch.zeros_like(weights)), None, None, None, None
+
+
+def ledger_total(vals, weights, mask, extras, state):
+    """Weighted total of the stacked loss values `vals`, recorded in the ledger `state` (spe_amd.steplog.StepLedger.record)."""
+    return _LedgerTotal.apply(vals, weights, mask, tuple(extras), state)
