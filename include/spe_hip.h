@@ -550,6 +550,22 @@ int spe_pos_learned_bwd(const float* g, float* d_col, float* d_row, int B, int h
 int spe_nms_sorted(const float* boxes, const long* labels, const int* counts, unsigned char* keep, int nimg, int nmax,
                    float iou_threshold, spe_stream_t stream);
 
+/* ---- detection head (csrc/detect.hip): the detections of a batch in ONE launch - what PostProcess
+ * (reference models/conditional_detr.py:592-623) followed by the per-class NMS above computes, without a host read.  One workgroup
+ * per image, four phases, nothing goes to HBM between them:
+ *   select   the top k of the N = Q * Kc logits of the image, ordered by logit descending, equal logits by flat index ascending.  The
+ *            order is that of an order-preserving uint32 image of the float: -0.0 counts as +0.0, every NaN lies above +inf;
+ *   decode   label = idx % Kc, query = idx / Kc; box = max(cxcywh -> xyxy, 0) * (w, h, w, h) in PostProcess's fp32 operations, one
+ *            rounding each (no contraction); sizes[b] = (h, w);
+ *   order    stable by label ascending: the order spe_nms_sorted expects;
+ *   suppress (do_nms != 0) greedy per class, IoU > iou_threshold in spe_nms_sorted's arithmetic; survivors move to the front.
+ * Outputs, every element written: out_logit [B][k] (the selected logits themselves, bit for bit), out_label [B][k] (int64), out_box
+ * [B][k][4] xyxy absolute, out_query [B][k] (source query), out_count [B]; rows count .. k-1 hold logit -inf, label -1, box 0, query -1.
+ * Integer LDS atomics only and every tie broken by index: bitwise reproducible.
+ * Returns -3 when k < 1 or k > N (torch.topk raises), -2 when k > 1024 or N > 2^20; B <= 0: nothing to do. */
+int spe_detect(const float* logits, const float* boxes, const float* sizes, int B, int Q, int Kc, int k, float iou_threshold,
+               int do_nms, float* out_logit, long* out_label, float* out_box, int* out_query, int* out_count, spe_stream_t stream);
+
 /* ---- CAM -> pseudo boxes (reference cams_deit.py:9-13 resize_cam, :61-96 get_multi_bboxes; engine.py:356-398).
  * spe_cam_prepare (device): M class maps cams[M][h][w] -> thresholded uint8 images out[M][rows][cols]: bilinear resize
  * (cv2.INTER_LINEAR convention), min-max normalisation, (x*255) truncated to uint8, THRESH_TOZERO at

@@ -26,7 +26,9 @@ EXTRA_FLAGS = {"attn_flash_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # img_resample.hip restates Pillow's fp64 coefficient arithmetic in a fixed operation order
                "img_resample.hip": ["-ffp-contract=off"],
                # step_ledger.hip restates Python's sum() over fp32 loss tensors: each product v * w is rounded before it is added, never fused
-               "step_ledger.hip": ["-ffp-contract=off"]}
+               "step_ledger.hip": ["-ffp-contract=off"],
+               # detect.hip restates PostProcess's fp32 box arithmetic and the NMS overlap test as elementwise compositions: one rounding per operation
+               "detect.hip": ["-ffp-contract=off"]}
 
 
 def flags_for(src):

@@ -5,7 +5,10 @@ after the optimizer step.  Signature, log lines and return value are the referen
 
 Difference: a weighted total that is not finite stops the run at the next log line or at the end of the epoch
 (FloatingPointError from the ledger), not before the optimizer step of that iteration; up to print_freq steps of compute are wasted,
-the weights are lost either way (the reference exits without saving)."""
+the weights are lost either way (the reference exits without saving).
+
+The evaluation loops `evaluate_det_voc` (reference engine_loc.py:127-201) and `evaluate_refinements` (engine.py:617-724) follow: the
+detection head (spe_amd.infer.detect) between the forward and a detection meter (spe_amd.evalmetrics), DESIGN.md section 8k."""
 import copy
 import time
 
@@ -104,3 +107,128 @@ def train_one_epoch_refine(model, criterion, data_loader, optimizer, device, epo
     stats = ledger.global_avg()                  # synchronised between the ranks; raises if a step's total was not finite
     print("Averaged stats:", ledger)
     return stats
+
+
+# ---- evaluation loops (reference engine_loc.py:127-201, engine.py:617-724) -----------------------------------
+# One forward, one detection-head launch (infer.detect) and one meter update per batch; nothing on a device tensor is read on the host
+# inside the batch loop.  The image id that looks the ground truth up is read from the loader's HOST tensor before the targets move
+# to the device; the meters get the id as a 0-d device tensor.
+def _host_id(t, key):
+    return int(t[key])                            # the loader's tensors live on the host: a read, not a synchronisation
+
+
+def _lookup(base_ds):
+    if base_ds is None:
+        raise ValueError("base_ds: a mapping or a callable from image id to the ground-truth dict of the meter (evalmetrics.py)")
+    return base_ds if callable(base_ds) else base_ds.__getitem__
+
+
+def _coco_cat_ids(base_ds):
+    """The category ids of the run: base_ds.getCatIds() (the COCO API's name) or base_ds.cat_ids, else every label of a mapping."""
+    if hasattr(base_ds, "getCatIds"):
+        return list(base_ds.getCatIds())
+    if hasattr(base_ds, "cat_ids"):
+        return list(base_ds.cat_ids)
+    if hasattr(base_ds, "values"):
+        return sorted({int(c) for g in base_ds.values() for c in torch.as_tensor(g["labels"]).reshape(-1).tolist()})
+    raise ValueError("evaluate_refinements: a callable base_ds needs .cat_ids (or .getCatIds())")
+
+
+@torch.no_grad()
+def evaluate_det_voc(model, criterion, postprocessors, data_loader, base_ds, device, output_dir, cache_dir, with_flip=False, *kargs,
+                     **kwargs):
+    """engine_loc.py:127-201 with the VOC meter in place of the result files: top 300, per-class NMS at 0.5, AP (VOC07 11-point unless
+    use_07_metric=False is passed) and CorLoc, printed in the lines of datasets/voc_voc.py:_eval_discovery and _do_python_eval (without
+    the closing banner about the MATLAB code).  base_ds: image id (t['idx']) -> {'boxes' [g,4] annotation frame, 'labels' [g],
+    'difficult' [g]}.  The class names come from data_loader.dataset.classes when it has them ('__background__' skipped), the class
+    count from there or from num_classes= (20).  Writes no files; returns the meter's summary (the reference returns None)."""
+    from . import infer
+    from .evalmetrics import VOCDetectionMeter
+    from .util.misc import NestedTensor
+    model.eval()
+    criterion.eval()
+    ledger = StepLedger(delimiter="  ")
+    header = f"[{time.strftime('%Y-%m-%d-%H:%M:%S', time.localtime())}] => Test:"
+    names = [c for c in getattr(getattr(data_loader, "dataset", None), "classes", ()) if c != "__background__"]
+    C = len(names) or int(kwargs.get("num_classes", 20))
+    names = names or [f"class{c + 1}" for c in range(C)]
+    use_07_metric = bool(kwargs.get("use_07_metric", True))
+    meter = VOCDetectionMeter(num_classes=C, ovthresh=0.5, file_roundtrip=True)
+    gt_of = _lookup(base_ds)
+    for samples, targets in ledger.log_every(data_loader, 256, header):
+        ids = [_host_id(t, "idx") for t in targets]
+        samples = samples.to(device)
+        batch_size = samples.tensors.shape[0]
+        targets = [{k: v.to(device) for k, v in t.items()} for t in targets]
+        if with_flip:
+            coupled = NestedTensor(torch.cat((samples.tensors, samples.tensors.flip(-1)), dim=0),
+                                   None if samples.mask is None else torch.cat((samples.mask, samples.mask.flip(-1)), dim=0))
+            outputs = infer.decouple_output(model(coupled)[0], bs=batch_size)
+        else:
+            outputs = model(samples)[0]
+        sizes = torch.stack([t["image_size"].flip(0) for t in targets], dim=0)
+        det = infer.detect(outputs, sizes, 300, 0.5)
+        meter.update(det.padded(), [{**gt_of(i), "image_id": t["idx"].reshape(())} for i, t in zip(ids, targets)])
+    meter.merge()
+    out = meter.summarize(use_07_metric=use_07_metric)
+    for what, per_class, mean in (("CorLoc", out["corloc"].tolist(), out["mean_corloc"]), ("AP", out["ap"].tolist(), out["map"])):
+        if what == "AP":
+            print("VOC07 metric? " + ("Yes" if use_07_metric else "No"))
+        for name, v in zip(names, per_class):
+            print("{} for {} = {:.4f}".format(what, name, v))
+        print("Mean {} = {:.4f}".format(what, mean))
+        print("~~~~~~~~")
+        print("Results:")
+        for v in per_class:
+            print("{:.3f}".format(v))
+        print("{:.3f}".format(mean))
+        print("~~~~~~~~")
+    return out
+
+
+_COCO_LINES = (("Precision", "AP", "0.50:0.95", "all", 100), ("Precision", "AP", "0.50", "all", 100), ("Precision", "AP", "0.75", "all", 100),
+               ("Precision", "AP", "0.50:0.95", "small", 100), ("Precision", "AP", "0.50:0.95", "medium", 100),
+               ("Precision", "AP", "0.50:0.95", "large", 100), ("Recall", "AR", "0.50:0.95", "all", 1), ("Recall", "AR", "0.50:0.95", "all", 10),
+               ("Recall", "AR", "0.50:0.95", "all", 100), ("Recall", "AR", "0.50:0.95", "small", 100),
+               ("Recall", "AR", "0.50:0.95", "medium", 100), ("Recall", "AR", "0.50:0.95", "large", 100))
+
+
+@torch.no_grad()
+def evaluate_refinements(model, criterion, postprocessors, data_loader, base_ds, device, output_dir, refine_stage=0):
+    """engine.py:617-724 for 'bbox': the last auxiliary output of refinement stage `refine_stage`, its losses in the step ledger (scaled,
+    `_unscaled`, class_error with window 1), top 100, per-class NMS at 0.5, the COCO meter.  base_ds: image id (t['image_id']) ->
+    {'boxes' [g,4] xywh, 'labels' [g], 'iscrowd' [g], 'area' [g]}; the category ids are base_ds.getCatIds() / base_ds.cat_ids, or every
+    label of a mapping.  -> (stats, meter): the global averages of the ledger plus stats['coco_eval_bbox'], COCOeval's twelve numbers."""
+    from . import infer
+    from .evalmetrics import COCODetectionMeter
+    for k in ("segm", "panoptic"):
+        if k in postprocessors:
+            raise NotImplementedError(f"evaluate_refinements: the {k!r} post-processor is outside this package (DESIGN.md section 7)")
+    model.eval()
+    criterion.eval()
+    ledger = StepLedger(windows={"class_error": 1}, fmts={"class_error": "{value:.2f}"}, delimiter="  ")
+    meter = COCODetectionMeter(_coco_cat_ids(base_ds))
+    gt_of = _lookup(base_ds)
+    for samples, targets in ledger.log_every(data_loader, 10, "Test:"):
+        ids = [_host_id(t, "image_id") for t in targets]
+        samples = samples.to(device)
+        targets = [{k: v.to(device) for k, v in t.items()} for t in targets]
+        outputs = model(samples)[refine_stage]["aux_outputs"][-1]
+        loss_criterion = copy.deepcopy(criterion.losses)
+        criterion.losses = ["labels", "boxes", "cardinality"]
+        try:
+            loss_dict = criterion(outputs, targets)
+        finally:
+            criterion.losses = loss_criterion
+        ledger.record(loss_dict, criterion.weight_dict)
+        orig_target_sizes = torch.stack([t["orig_size"] for t in targets], dim=0)
+        det = infer.detect(outputs, orig_target_sizes, 100, 0.5)
+        meter.update(det.padded(), [{**gt_of(i), "image_id": t["image_id"].reshape(())} for i, t in zip(ids, targets)])
+    stats = ledger.global_avg()                  # synchronised between the ranks
+    print("Averaged stats:", ledger)
+    meter.merge()
+    numbers = meter.summarize()["stats"]
+    for (title, short, iou, area, dets), v in zip(_COCO_LINES, numbers):
+        print(" {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}".format("Average " + title, f"({short})", iou, area, dets, v))
+    stats["coco_eval_bbox"] = numbers.tolist()
+    return stats, meter

@@ -1,10 +1,16 @@
 """Inference-side post-processing of the SPE detector: the tensor work of
 reference engine_loc.py:99-124 (`decouple_output`, flip test-time augmentation) and engine_loc.py:150-174
 (`postprocessors['bbox'](outputs, sizes, 300)` followed by per-class torchvision NMS at IoU 0.5).
+
+`per_class_nms` takes PostProcess's list; `detect` is the two steps in one HIP launch without a host read (csrc/detect.hip), which is
+what the evaluation loops of spe_amd.engine call.  CUDA tensors take the kernels; CPU tensors take the same rules composed of torch /
+numpy operations (the pattern of spe_amd.evalmetrics), which is what the host logic is tested with.
 """
+import numpy as np
 import torch
 
 from . import kernels as K
+from .util import box_ops
 
 _COMBINE = ("pred_logits", "pred_boxes", "x_logits", "x_cls_logits", "cams_cls", "aux_outputs")
 
@@ -36,7 +42,9 @@ def decouple_output(output, bs=2):
 def per_class_nms(results, iou_threshold=0.5):
     """results: list (one per image) of {'scores' [n], 'labels' [n], 'boxes' [n,4] xyxy} as returned by PostProcess.
     Returns the list the reference builds at engine_loc.py:154-174: for every predicted class in ascending order the
-    NMS survivors in descending score order.  One sort + one HIP launch for the whole batch, no per-class host loop."""
+    NMS survivors in descending score order.  One sort + one HIP launch for the whole batch, no per-class host loop (CPU tensors: the
+    same order and a numpy restatement of the launch).  The boolean-mask indexing at the end reads back from the device, three times per
+    image; `detect` below does not."""
     if not results:
         return results
     n = results[0]["scores"].numel()
@@ -51,9 +59,114 @@ def per_class_nms(results, iou_threshold=0.5):
     sl = labels.gather(1, order).contiguous()
     sb = boxes.gather(1, order[..., None].expand(-1, -1, 4)).contiguous()
     ss = scores.gather(1, order)
-    keep = K.nms_sorted(sb, sl, iou_threshold)
+    keep = K.nms_sorted(sb, sl, iou_threshold) if sb.is_cuda else _nms_sorted_host(sb, sl, iou_threshold)
     out = []
     for i in range(len(results)):
         m = keep[i]
         out.append({"scores": ss[i][m], "labels": sl[i][m], "boxes": sb[i][m]})
     return out
+
+
+def _nms_sorted_host(boxes, labels, iou_threshold):
+    """kernels.nms_sorted on CPU tensors: the same visit order and the same fp32 arithmetic, one rounding per operation (numpy)."""
+    bx, lb = boxes.numpy(), labels.numpy()
+    I, n = lb.shape
+    keep = np.ones((I, n), dtype=bool)
+    thr = np.float32(iou_threshold)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for img in range(I):
+            b, l = bx[img], lb[img]
+            assert (np.diff(l) >= 0).all(), "detections must be ordered by label"
+            end = np.searchsorted(l, l, side="right")                           # one past the last detection of the label
+            area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+            for i in range(n):
+                if not keep[img, i] or i + 1 >= end[i]:
+                    continue
+                s = slice(i + 1, end[i])
+                w = np.maximum(np.minimum(b[i, 2], b[s, 2]) - np.maximum(b[i, 0], b[s, 0]), np.float32(0))
+                h = np.maximum(np.minimum(b[i, 3], b[s, 3]) - np.maximum(b[i, 1], b[s, 1]), np.float32(0))
+                inter = w * h
+                keep[img, s] &= ~(inter / (area[i] + area[s] - inter) > thr)
+    return torch.from_numpy(keep)
+
+
+# ---- the detection head: PostProcess + per_class_nms in one launch (csrc/detect.hip; DESIGN.md section 8k) ---------------------------
+def select_key(logits):
+    """The order the head selects by, as int64: an order-preserving image of the fp32 logit in which -0.0 counts as +0.0 and every NaN
+    lies above +inf (torch.topk's order).  Greater key = better; equal keys are taken in ascending flat index."""
+    u = logits.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    u = torch.where(u == 0x80000000, torch.zeros_like(u), u)
+    key = torch.where((u & 0x80000000) != 0, ~u & 0xFFFFFFFF, u | 0x80000000)
+    return torch.where(nan, torch.full_like(u, 0xFFFFFFFF), key)
+
+
+def _detect_host(logits, boxes, sizes, k, iou_threshold, nms):
+    """kernels.detect on CPU tensors, composed of torch operations: the same selection rule, PostProcess's box arithmetic, the order and
+    the suppression of per_class_nms.  The same five results, and the scores as a sixth."""
+    B, Q, Kc = logits.shape
+    if k < 1 or k > Q * Kc:
+        raise ValueError(f"detect: k = {k} out of range for {Q * Kc} = {Q} x {Kc} scores per image")
+    if k > K.DETECT_MAX_K or Q * Kc > K.DETECT_MAX_N:
+        raise ValueError(f"detect: at most k = {K.DETECT_MAX_K} of at most {K.DETECT_MAX_N} scores per image")
+    flat = logits.reshape(B, -1)
+    idx = torch.sort(select_key(flat), dim=1, descending=True, stable=True).indices[:, :k]
+    query, label = torch.div(idx, Kc, rounding_mode="floor"), idx % Kc
+    xyxy = box_ops.box_cxcywh_to_xyxy(boxes).clamp(min=0)
+    xyxy = torch.gather(xyxy, 1, query.unsqueeze(-1).repeat(1, 1, 4))
+    img_h, img_w = sizes.unbind(1)
+    xyxy = xyxy * torch.stack([img_w, img_h, img_w, img_h], dim=1)[:, None, :]
+    order = torch.sort(label, dim=1, stable=True).indices                      # the list is score-descending already
+    label, query = label.gather(1, order), query.gather(1, order)
+    logit = flat.gather(1, idx).gather(1, order)
+    # PostProcess's own scores: out of the sigmoid of the whole tensor (ATen's CPU sigmoid of a short tensor can differ in the last bit)
+    score = logits.sigmoid().reshape(B, -1).gather(1, idx).gather(1, order)
+    xyxy = xyxy.gather(1, order[..., None].expand(-1, -1, 4)).contiguous()
+    keep = _nms_sorted_host(xyxy, label, iou_threshold) if nms else torch.ones((B, k), dtype=torch.bool)
+    front = torch.sort((~keep).to(torch.uint8), dim=1, stable=True).indices     # survivors first, in their order
+    keep = keep.gather(1, front)
+    out_logit = torch.where(keep, logit.gather(1, front), torch.full_like(logit, float("-inf")))
+    out_label = torch.where(keep, label.gather(1, front), torch.full_like(label, -1))
+    out_query = torch.where(keep, query.gather(1, front), torch.full_like(query, -1)).to(torch.int32)
+    out_box = torch.where(keep[..., None], xyxy.gather(1, front[..., None].expand(-1, -1, 4)), torch.zeros_like(xyxy))
+    out_score = torch.where(keep, score.gather(1, front), torch.zeros_like(score))
+    return out_logit, out_label, out_box, out_query, keep.sum(1).to(torch.int32), out_score
+
+
+class Detections:
+    """What `detect` returns: per image k rows, the `counts[i]` detections in front - (label ascending, score descending), the order of
+    per_class_nms - and a tail of score 0, label -1, box 0, query -1.  All members are tensors on the device of the inputs.
+
+    scores [B,k] (on the device torch.sigmoid of the selected logits, one ATen launch, so bitwise PostProcess's value of that element;
+    the host path hands in PostProcess's own values), logits [B,k], labels [B,k] int64, boxes [B,k,4] xyxy in absolute pixels, queries
+    [B,k] int32 (the source query of every row), counts [B] int32."""
+
+    def __init__(self, logits, labels, boxes, queries, counts, scores=None):
+        self.logits, self.labels, self.boxes, self.queries, self.counts = logits, labels, boxes, queries, counts
+        self.scores = torch.sigmoid(logits) if scores is None else scores       # the tail: sigmoid(-inf) = 0
+
+    def padded(self):
+        """One dict {'scores','labels','boxes'} per image: views with exactly k rows, no host read.  Both detection meters drop labels
+        outside their range, so the list goes straight into `meter.update()`."""
+        return [{"scores": s, "labels": l, "boxes": b} for s, l, b in zip(self.scores, self.labels, self.boxes)]
+
+    def results(self):
+        """The list the reference's loops build (per_class_nms's), trimmed to `counts`: ONE host copy of the B counts."""
+        return [{"scores": s[:c], "labels": l[:c], "boxes": b[:c]}
+                for s, l, b, c in zip(self.scores, self.labels, self.boxes, self.counts.tolist())]
+
+
+@torch.no_grad()
+def detect(outputs, target_sizes, keep_queries=100, iou_threshold=0.5, nms=True):
+    """outputs: {'pred_logits' [B,Q,Kc], 'pred_boxes' [B,Q,4]}; target_sizes [B,2] (h, w) -> Detections.  With nms=True `.results()` is
+    per_class_nms(PostProcess()(outputs, target_sizes, keep_queries), iou_threshold); with nms=False it is PostProcess's list in
+    (label, score) order.  Equal scores are taken in ascending (query, class) order, where torch.topk promises nothing.  On the device:
+    one HIP launch plus the sigmoid of the [B,k] selected logits, no host read; CPU tensors take the same rules composed of torch
+    operations."""
+    logits, boxes = outputs["pred_logits"], outputs["pred_boxes"]
+    assert len(logits) == len(target_sizes) and target_sizes.shape[1] == 2
+    logits, boxes = logits.float().contiguous(), boxes.float().contiguous()
+    sizes = target_sizes.to(device=logits.device, dtype=torch.float32).contiguous()
+    if logits.is_cuda:
+        return Detections(*K.detect(logits, boxes, sizes, keep_queries, iou_threshold, nms))
+    return Detections(*_detect_host(logits, boxes, sizes, int(keep_queries), iou_threshold, nms))

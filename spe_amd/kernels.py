@@ -1639,6 +1639,40 @@ def nms_sorted(boxes, labels, iou_threshold, counts=None):
     return keep.bool()
 
 
+DETECT_MAX_K, DETECT_MAX_N = 1024, 1 << 20       # csrc/detect.hip: DET_MAXK, DET_MAXN
+
+
+def detect(logits, boxes, sizes, k, iou_threshold, nms=True, out=None):
+    """The detection head in one launch (csrc/detect.hip): logits [B,Q,Kc], boxes [B,Q,4] normalised cxcywh, sizes [B,2] (h, w), all
+    fp32 -> (logit [B,k], label [B,k] int64, box [B,k,4] xyxy absolute, query [B,k] int32, count [B] int32): per image the top k logits
+    in (label ascending, logit descending) order, the NMS survivors in front when `nms`; rows count .. k-1 hold -inf / -1 / 0 / -1.
+    out: the five buffers of an earlier call (every element is overwritten).  Nothing is read back."""
+    _chk(logits, boxes, sizes)
+    B, Q, Kc = logits.shape
+    N, k = Q * Kc, int(k)
+    if k < 1 or k > N:
+        raise ValueError(f"detect: k = {k} out of range for {N} = {Q} x {Kc} scores per image")       # torch.topk raises too
+    if k > DETECT_MAX_K or N > DETECT_MAX_N:
+        raise ValueError(f"detect: at most k = {DETECT_MAX_K} of at most {DETECT_MAX_N} scores per image (k = {k}, Q * Kc = {N})")
+    if boxes.shape != (B, Q, 4) or sizes.shape != (B, 2):
+        raise ValueError(f"detect: boxes {tuple(boxes.shape)} / sizes {tuple(sizes.shape)} do not fit logits {tuple(logits.shape)}")
+    if not (logits.is_contiguous() and boxes.is_contiguous() and sizes.is_contiguous()):
+        raise ValueError("detect: contiguous tensors only")
+    dev = logits.device
+    if out is None:
+        out = (torch.empty((B, k), device=dev, dtype=torch.float32), torch.empty((B, k), device=dev, dtype=torch.int64),
+               torch.empty((B, k, 4), device=dev, dtype=torch.float32), torch.empty((B, k), device=dev, dtype=torch.int32),
+               torch.empty((B,), device=dev, dtype=torch.int32))
+    logit, label, box, query, count = out
+    want = (((B, k), torch.float32), ((B, k), torch.int64), ((B, k, 4), torch.float32), ((B, k), torch.int32), ((B,), torch.int32))
+    for t, (shape, dt) in zip(out, want):
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError("detect: `out` must be the five contiguous buffers of an earlier call with the same B and k")
+    _call("spe_detect", _p(logits), _p(boxes), _p(sizes), B, Q, Kc, k, float(iou_threshold), 1 if nms else 0, _p(logit), _p(label),
+          _p(box), _p(query), _p(count), _st())
+    return logit, label, box, query, count
+
+
 # ---- CAM -> pseudo boxes -------------------------------------------------------------------------
 def cam_prepare(maps, rows, cols, cam_thr):
     """maps [M,h,w] fp32 (device) -> thresholded uint8 images [M,rows,cols] (device); see csrc/cambox.hip."""
