@@ -41,7 +41,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_coco_match / spe_coco_accumulate (the COCO AP / AR tables on the device),
  * spe_resample_plan / _tables / _h / _v (the input transforms: Pillow-exact bilinear resize, crop, flip, normalise, pad),
  * spe_ledger_state_bytes / _record / _total_bwd / _summary (the step ledger: weighted total, loss meters and non-finite guard on the device)
- * - 99 entry points */
+ * spe_gemm_f32_plan (the kernel selection and launch choices of spe_gemm_f32 / spe_gemm_ex, host only)
+ * - 100 entry points */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -98,6 +99,19 @@ int spe_gemm_ex(const void* A, int a_bf16, const float* B, float* C, const float
 
 /* Tile edge (128 or 64) spe_gemm_* will use for an (M, N, batch) problem; callers use it to choose split-K. */
 int spe_gemm_tile(int M, int N, int nbatch);
+/* spe_gemm_f32_plan: which instance of spe_gemm_kernel<T, TA, TB, SPLIT> spe_gemm_f32 / spe_gemm_ex run for a problem and every launch
+ * choice that goes with it.  Host only: no device, no stream, nothing is launched; the launcher calls the same function, so tests and
+ * tools can tell which kernel and which load / tile-order path a shape exercises.  The arguments are those of spe_gemm_ex that influence
+ * the choice; epilogue = 1 when a bias, an activation or C2 is asked for; a_mod16 / b_mod16 are the addresses of A / B modulo 16.
+ * v[11] = { T (tile edge), TA, TB, SPLIT, splitk (effective: a request above the number of 32-wide k-tiles is clamped to it), kt_per_split
+ * (k-tiles per split; the last splits may get fewer, or none), slab (floats between the slabs of a splitk < 0 launch, else 0), vecA, vecB
+ * (16-byte operand loads: base aligned - 8 bytes for a bf16 A - and leading dimension and batch strides multiples of 4), xcd_bind (0 plain
+ * tile order, 1 / 2: M / N panels bound to XCDs), grid.x (tiles plus padding workgroups) }; all zero when M, N or a batch count is <= 0
+ * (nothing to do).  Returns the status spe_gemm_ex would return: -4 (K <= 0), -2 (transA and transB), -5 (more slabs than k-tiles), -3
+ * (splitk > 1 with an epilogue), else 0. */
+int spe_gemm_f32_plan(int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB, int batch0, int batch1,
+                      long sA0, long sA1, long sB0, long sB1, long sC0, long sC1, int splitk, int precision, int a_bf16,
+                      int epilogue, int a_mod16, int b_mod16, long* v);
 
 /* ---- LayerNorm (nn.LayerNorm; reference models/cait.py:403,407 eps 1e-6,
  * models/transformer.py:264-265,342-344 eps 1e-5).  C % 4 == 0, C <= 1024.

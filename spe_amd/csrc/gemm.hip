@@ -400,25 +400,6 @@ __global__ __launch_bounds__(256) void spe_gemm_kernel(GemmArgs p) {
     }
 }
 
-template <int T, bool TA, bool TB, bool SPLIT>
-static int launch_gemm_t(const GemmArgs& p, int nbatch, hipStream_t stream) {
-    constexpr int smem = 2 * 2 * (SPLIT ? 2 : 1) * T * LDSLD * (int)sizeof(unsigned short);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spe_gemm_kernel<T, TA, TB, SPLIT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    const TileOrder order = tile_order(p.M, p.N, (p.M + T - 1) / T, (p.N + T - 1) / T);
-    GemmArgs q = p;
-    q.xcd_bind = order.xcd_bind;
-    dim3 grid(order.grid, 1, nbatch * p.splitk);
-    hipLaunchKernelGGL((spe_gemm_kernel<T, TA, TB, SPLIT>), grid, dim3(256), smem, stream, q);
-    SPE_CHECK_LAUNCH();
-    return 0;
-}
-
 // Tile choice: every GEMM of this model is HBM/latency bound, so what matters is enough workgroups in flight.
 // 128x128 tiles when they already give >= 1 workgroup per CU (split-K slices count), 64x64 tiles (4x the
 // workgroups, half the registers, twice the L2 re-reads) otherwise and for skinny outputs (N <= 64: the per-head attention contractions).
@@ -430,10 +411,75 @@ extern "C" int spe_gemm_tile(int M, int N, int nbatch) {
     return (t128 >= 256 && N > 64 && M > 64) ? 128 : 64;
 }
 
+// The argument checks and every launch choice of spe_gemm_ex, in one place: the launcher fills GemmArgs and the grid from the answer,
+// spe_gemm_f32_plan hands it to tests and tools (tests/test_f32_gemm_plan_cpu.py pins it).  Status as the launcher returns it; 1 = nothing
+// to do (an empty M, N or batch: the launcher returns 0 without a launch).  epilogue: bias, activation or C2 asked for.  a_mod16 / b_mod16:
+// the operand addresses modulo 16.
+struct GemmPlan { int T, TA, TB, SPLIT, splitk, kt_per_split; long slab; int vecA, vecB, xcd_bind, grid; };
+static int gemm_f32_select(int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB, int batch0, int batch1,
+                           long sA0, long sA1, long sB0, long sB1, long sC0, long sC1, int splitk, int precision, int a_bf16,
+                           int epilogue, int a_mod16, int b_mod16, GemmPlan* s) {
+    if (M <= 0 || N <= 0 || K <= 0 || batch0 <= 0 || batch1 <= 0) return K <= 0 && M > 0 && N > 0 ? -4 : 1;
+    if (transA && transB) return -2;  // not needed on this path
+    s->TA = transA ? 1 : 0; s->TB = transB ? 1 : 0; s->SPLIT = precision == 1;
+    s->slab = 0;
+    const int ktiles = (K + BK - 1) / BK;
+    if (splitk < 0) {           // slab mode: C must hold |splitk| slabs (M*ldc floats; batched: the extent of all batches)
+        splitk = -splitk;
+        s->slab = (batch0 * batch1 == 1) ? (long)M * ldc
+                                         : ((((long)(batch0 - 1) * sC0 + (long)(batch1 - 1) * sC1 + (long)(M - 1) * ldc + N) + 3) & ~3L);
+        if (splitk > ktiles) return -5;
+    }
+    if (splitk < 1) splitk = 1;
+    if (splitk > ktiles) splitk = ktiles > 0 ? ktiles : 1;
+    s->kt_per_split = (ktiles + splitk - 1) / splitk;
+    s->splitk = splitk;
+    if (splitk > 1 && epilogue) return -3;
+    auto m4 = [](long v) { return (v & 3) == 0; };
+    // float4 loads need 16-B aligned rows; quads that straddle an edge fall back to scalars
+    s->vecA = ((a_bf16 ? (a_mod16 & 7) : (a_mod16 & 15)) == 0) && m4(lda) && m4(sA0) && m4(sA1);
+    s->vecB = ((b_mod16 & 15) == 0) && m4(ldb) && m4(sB0) && m4(sB1);
+    s->T = spe_gemm_tile(M, N, batch0 * batch1 * splitk);
+    const TileOrder order = tile_order(M, N, (M + s->T - 1) / s->T, (N + s->T - 1) / s->T);
+    s->xcd_bind = order.xcd_bind;
+    s->grid = order.grid;
+    return 0;
+}
+
+template <int T, bool TA, bool TB, bool SPLIT>
+static int launch_gemm_t(const GemmArgs& p, int grid_x, int nbatch, hipStream_t stream) {
+    constexpr int smem = 2 * 2 * (SPLIT ? 2 : 1) * T * LDSLD * (int)sizeof(unsigned short);
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spe_gemm_kernel<T, TA, TB, SPLIT>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+    dim3 grid(grid_x, 1, nbatch * p.splitk);
+    hipLaunchKernelGGL((spe_gemm_kernel<T, TA, TB, SPLIT>), grid, dim3(256), smem, stream, p);
+    SPE_CHECK_LAUNCH();
+    return 0;
+}
+
 template <bool TA, bool TB, bool SPLIT>
-static int launch_gemm(const GemmArgs& p, int nbatch, hipStream_t stream) {
-    if (spe_gemm_tile(p.M, p.N, nbatch * p.splitk) == 128) return launch_gemm_t<128, TA, TB, SPLIT>(p, nbatch, stream);
-    return launch_gemm_t<64, TA, TB, SPLIT>(p, nbatch, stream);
+static int launch_gemm(const GemmArgs& p, const GemmPlan& s, int nbatch, hipStream_t stream) {
+    if (s.T == 128) return launch_gemm_t<128, TA, TB, SPLIT>(p, s.grid, nbatch, stream);
+    return launch_gemm_t<64, TA, TB, SPLIT>(p, s.grid, nbatch, stream);
+}
+
+// C-ABI: see include/spe_hip.h (spe_gemm_f32_plan).  Host only: the selection for a problem, no device needed.
+extern "C" int spe_gemm_f32_plan(int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB, int batch0, int batch1,
+                                 long sA0, long sA1, long sB0, long sB1, long sC0, long sC1, int splitk, int precision, int a_bf16,
+                                 int epilogue, int a_mod16, int b_mod16, long* v) {
+    GemmPlan s;
+    const int rc = gemm_f32_select(M, N, K, lda, ldb, ldc, transA, transB, batch0, batch1, sA0, sA1, sB0, sB1, sC0, sC1, splitk, precision,
+                                   a_bf16, epilogue, a_mod16, b_mod16, &s);
+    if (rc < 0) return rc;
+    if (rc > 0) s = GemmPlan{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};             // nothing to do: no kernel runs
+    if (v) { v[0] = s.T; v[1] = s.TA; v[2] = s.TB; v[3] = s.SPLIT; v[4] = s.splitk; v[5] = s.kt_per_split; v[6] = s.slab;
+             v[7] = s.vecA; v[8] = s.vecB; v[9] = s.xcd_bind; v[10] = s.grid; }
+    return 0;
 }
 
 extern "C" int spe_gemm_ex(const void* A, int a_bf16, const float* B, float* C, const float* bias, float* C2,
@@ -455,33 +501,20 @@ extern "C" int spe_gemm_ex(const void* A, int a_bf16, const float* B, float* C, 
                            int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB,
                            int batch0, int batch1, long sA0, long sA1, long sB0, long sB1, long sC0, long sC1,
                            float alpha, int act, int splitk, int precision, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || batch0 <= 0 || batch1 <= 0) return K <= 0 && M > 0 && N > 0 ? -4 : 0;
-    if (transA && transB) return -2;  // not needed on this path
+    GemmPlan s;
+    const int rc = gemm_f32_select(M, N, K, lda, ldb, ldc, transA, transB, batch0, batch1, sA0, sA1, sB0, sB1, sC0, sC1, splitk, precision,
+                                   a_bf16, act != 0 || C2 != nullptr || bias != nullptr, (int)(reinterpret_cast<uintptr_t>(A) & 15),
+                                   (int)(reinterpret_cast<uintptr_t>(B) & 15), &s);
+    if (rc != 0) return rc > 0 ? 0 : rc;
     GemmArgs p;
     p.A = reinterpret_cast<const float*>(A); p.a_bf16 = a_bf16; p.B = B; p.C = C; p.C2 = C2; p.bias = bias;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.nb1 = batch1; p.sA0 = sA0; p.sA1 = sA1; p.sB0 = sB0; p.sB1 = sB1; p.sC0 = sC0; p.sC1 = sC1;
-    p.alpha = alpha; p.act = act; p.slab = 0;
-    const int ktiles = (K + BK - 1) / BK;
-    if (splitk < 0) {           // slab mode: C must hold |splitk| slabs (M*ldc floats; batched: the extent of all batches)
-        splitk = -splitk;
-        p.slab = (batch0 * batch1 == 1) ? (long)M * ldc
-                                        : ((((long)(batch0 - 1) * sC0 + (long)(batch1 - 1) * sC1 + (long)(M - 1) * ldc + N) + 3) & ~3L);
-        if (splitk > ktiles) return -5;
-    }
-    if (splitk < 1) splitk = 1;
-    if (splitk > ktiles) splitk = ktiles > 0 ? ktiles : 1;
-    p.kt_per_split = (ktiles + splitk - 1) / splitk;
-    p.splitk = splitk;
-    if (splitk > 1 && (act != 0 || C2 != nullptr || bias != nullptr)) return -3;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    auto m4 = [](long v) { return (v & 3) == 0; };
-    // float4 loads need 16-B aligned rows; quads that straddle an edge fall back to scalars
-    p.vecA = (a_bf16 ? ((reinterpret_cast<uintptr_t>(A) & 7) == 0) : al16(A)) && m4(lda) && m4(sA0) && m4(sA1);
-    p.vecB = al16(B) && m4(ldb) && m4(sB0) && m4(sB1);
+    p.alpha = alpha; p.act = act; p.slab = s.slab;
+    p.kt_per_split = s.kt_per_split; p.splitk = s.splitk;
+    p.vecA = s.vecA; p.vecB = s.vecB; p.xcd_bind = s.xcd_bind;
     const int nbatch = batch0 * batch1;
-    const bool split = precision == 1;
-    if (!transA && transB)  return split ? launch_gemm<false, true, true>(p, nbatch, stream) : launch_gemm<false, true, false>(p, nbatch, stream);
-    if (!transA && !transB) return split ? launch_gemm<false, false, true>(p, nbatch, stream) : launch_gemm<false, false, false>(p, nbatch, stream);
-    return split ? launch_gemm<true, false, true>(p, nbatch, stream) : launch_gemm<true, false, false>(p, nbatch, stream);
+    if (!s.TA && s.TB)  return s.SPLIT ? launch_gemm<false, true, true>(p, s, nbatch, stream) : launch_gemm<false, true, false>(p, s, nbatch, stream);
+    if (!s.TA && !s.TB) return s.SPLIT ? launch_gemm<false, false, true>(p, s, nbatch, stream) : launch_gemm<false, false, false>(p, s, nbatch, stream);
+    return s.SPLIT ? launch_gemm<true, false, true>(p, s, nbatch, stream) : launch_gemm<true, false, false>(p, s, nbatch, stream);
 }

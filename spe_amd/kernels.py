@@ -323,6 +323,24 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, transA=False, transB=False, bias=None,
     return C
 
 
+GEMM_PLAN_FIELDS = ("T", "TA", "TB", "SPLIT", "splitk", "kt_per_split", "slab", "vecA", "vecB", "xcd_bind", "grid_x")
+
+
+def gemm_plan(M, N, K, lda, ldb, ldc, transA=False, transB=False, batch0=1, batch1=1, sA=(0, 0), sB=(0, 0), sC=(0, 0), splitk=1,
+              precision=0, a_bf16=False, epilogue=False, a_mod16=0, b_mod16=0):
+    """Which instance gemm / gemm_bf16a run for a problem and how they launch it (spe_gemm_f32_plan, the launcher's own selection):
+    dict(T, TA, TB, SPLIT, splitk, kt_per_split, slab, vecA, vecB, xcd_bind, grid_x) - spe_gemm_kernel<T, TA, TB, SPLIT>, the effective
+    split, k-tiles per split, floats between slabs, the 16-byte load flags, the tile order and grid.x - or None where the launcher would
+    refuse.  epilogue: a bias, an activation or C2 is asked for; a_mod16 / b_mod16: operand addresses modulo 16.  Needs no device.  For
+    tests and tools: no hot path calls it."""
+    v = (ctypes.c_long * len(GEMM_PLAN_FIELDS))()
+    rc = lib.load().spe_gemm_f32_plan(M, N, K, lda, ldb, ldc, int(transA), int(transB), batch0, batch1, sA[0], sA[1], sB[0], sB[1],
+                                      sC[0], sC[1], int(splitk), int(precision), int(a_bf16), int(epilogue), int(a_mod16), int(b_mod16), v)
+    if rc != 0:
+        return None
+    return dict(zip(GEMM_PLAN_FIELDS, (int(x) for x in v)))
+
+
 # ---- nn.Linear ------------------------------------------------------------------------------
 # Benchmark ("bf16") precision, large row counts: the three GEMMs of a Linear run on bf16 copies of their operands
 # (csrc/gemm_bf16.hip) - the same roundings spe_gemm_f32 applies while staging, so the products are identical, with
