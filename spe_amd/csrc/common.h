@@ -76,6 +76,8 @@ __device__ __forceinline__ float spe_erff(float a) {
     const float small = fmaf(q, a, a);
     return t > 0.927734375f ? big : small;
 }
+// exact-erf GELU of the GEMM epilogues
+__device__ __forceinline__ float spe_gelu_erf(float x) { return 0.5f * x * (1.0f + spe_erff(x * 0.70710678118654752f)); }
 
 // Streaming stores (global_store ... nt) for the GEMM epilogues: outputs that the kernel never reads again - kept out of
 // the L2 they do not evict the operand panels nor leave dirty lines behind (same-box A/B: 65.6 -> 65.2 ms per step).  The

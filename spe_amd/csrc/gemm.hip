@@ -2,14 +2,21 @@
 //
 //   C[z][m][n] = act( alpha * sum_k opA(z)[m][k] * opB(z)[k][n] + bias[n] )
 //
-// fp32 tensors in HBM; operands are rounded to bf16 while they are staged into LDS and
+// fp32 tensors in HBM (A optionally bf16 bits); operands are rounded to bf16 while they are staged into LDS and
 // multiplied with v_mfma_f32_16x16x32_bf16 (fp32 accumulate).  `precision == 1` selects the
 // 3-term split (hi*hi + hi*lo + lo*hi) which recovers ~fp32 accuracy at 3x the MFMA work; it is
 // what the 1e-3 parity mode uses.  Replaces the implicit ATen GEMMs behind nn.Linear / torch.bmm
 // in reference models/cait.py:374-393, models/transformer.py:355-427, models/attention.py:353,375.
 //
-// Block = 256 threads = 4 waves (2x2); block tile 128x128x32; wave tile 64x64 = 4x4 MFMA tiles.
-// Register-staged double buffering: tile t+1 is in flight from HBM while tile t is multiplied.
+// One kernel, spe_gemm_kernel<T, TA, TB, SPLIT>, in the 12 instances of F32_GEMM_INSTANCES: block tile T x T x 32 with T = 128
+// or 64 (spe_gemm_tile chooses), NT / NN / TN operand layouts, plain or split.  Block = 256 threads = 4 waves (2x2); wave tile
+// T/2 x T/2 = (T/32)^2 MFMA tiles.  Register-staged double buffering: tile t+1 is in flight from HBM while tile t is multiplied.
+//   load   load_tile<KC, R, MASK>: HBM -> registers for either contiguous index, one overload per element type (fp32; A stored
+//          as bf16 bits).  Its contract when `vec` is set: rows are 16-B aligned (8-B for bf16) and padded to a multiple of 4 elements.
+//   stage  stage_kc / stage_rc: the two register -> LDS layouts, both through store_bf16 (rounding, hi / lo split).
+//   mult   the MFMAs are issued as (B-frag, A-frag), so they produce C^T tiles: each lane ends up with four CONSECUTIVE
+//          columns of one row of C, which the epilogue stores as one 16-B quad.
+//   store  alpha, bias, C2, activation; K splits add atomically or store their own slab.
 #include "common.h"
 #include "gemm_tiles.h"
 #include <stdlib.h>
@@ -39,205 +46,125 @@ struct GemmArgs {
 // `vec` (wave-uniform): rows are 16-B aligned and padded to a multiple of 4 floats, so a float4
 // at any 4-aligned in-row offset is inside the allocation even when it straddles the logical edge.
 //
-// "KC": the contraction index is the contiguous one: X(r,k) = base[r*ld + k].
-// thread t loads rows r = (t>>3) + 32*i, k-quad (t&7).
-template <int R, bool MASK>
-__device__ __forceinline__ void load_kc(const float* __restrict__ base, long ld, int row0, int nrows,
-                                        int k0, int kend, bool vec, float v[4][4]) {
+// Thread t of the 256 owns NI = R / 32 quads of an R x 32 operand tile: elements (s + STEP * i, c .. c + 3), i < NI, with c along the
+// contiguous index of the tensor and s along the strided one; the loaders read them into v[i][0..3].
+//   "KC", the contraction index is the contiguous one, X(r,k) = base[r*ld + k]:  k-quad t&7 of rows (t>>3) + 32 i
+//   "RC", the row (m or n) index is contiguous, X(r,k) = base[k*ld + r]:  R = 128: row-quad t>>3 at k = (t&7)*4 + i (i < 4)
+//                                                                         R =  64: row-quad (t>>3)&15 at k = (t&7)*4 + 2*(t>>7) + i (i < 2)
+// The clamp-then-mask rule of both loaders: the strided index is clamped to its last valid value, a quad starts at
+// min(c, (climit - 1) & ~3) (>= 0 since climit >= 1; without `vec` each element is clamped and loaded on its own), the mask tests the
+// UNCLAMPED indices.  !MASK: interior tile, 16-B aligned rows: no clamps, no selects (the staging VALU work bounds this kernel).
+template <bool KC, int R, bool MASK>
+__device__ __forceinline__ void load_tile(const float* __restrict__ base, long ld, int row0, int nrows, int k0, int kend, bool vec, float v[4][4]) {
     const int t = threadIdx.x;
-    const int k = k0 + (t & 7) * 4;
-    if (!MASK) {   // interior tile, 16-B aligned rows: no clamps, no selects (the staging VALU work bounds this kernel)
-        const float* p0 = base + (long)(row0 + (t >> 3)) * ld + k;
+    constexpr int NI = R / 32, STEP = KC ? 32 : 1;
+    const int c = KC ? k0 + (t & 7) * 4 : row0 + ((R == 128) ? (t >> 3) : ((t >> 3) & 15)) * 4;
+    const int sRC = KC ? 0 : k0 + (t & 7) * 4 + ((R == 128) ? 0 : 2 * (t >> 7));
+    auto s0 = [&]() { return KC ? row0 + (t >> 3) : sRC; };      // KC: formed where it is used, which keeps hipcc's instruction order
+    const int climit = KC ? kend : nrows, slimit = KC ? nrows : kend;
+    if (!MASK) {
+        const float* p0 = base + (long)s0() * ld + c;
 #pragma unroll
-        for (int i = 0; i < R / 32; ++i) {
-            const float4 q = *reinterpret_cast<const float4*>(p0 + (long)(32 * i) * ld);
+        for (int i = 0; i < NI; ++i) {
+            const float4 q = *reinterpret_cast<const float4*>(p0 + (long)(STEP * i) * ld);
             v[i][0] = q.x; v[i][1] = q.y; v[i][2] = q.z; v[i][3] = q.w;
         }
         return;
     }
-    const int kq = min(k, (kend - 1) & ~3);            // clamped quad start (>= 0 since kend >= 1)
-    if (vec) {
-#pragma unroll
-        for (int i = 0; i < R / 32; ++i) {
-            const int r = row0 + (t >> 3) + 32 * i;
-            const float4 q = *reinterpret_cast<const float4*>(base + (long)min(r, nrows - 1) * ld + kq);
-            const bool rv = r < nrows;
-            v[i][0] = (rv && k + 0 < kend) ? q.x : 0.f; v[i][1] = (rv && k + 1 < kend) ? q.y : 0.f;
-            v[i][2] = (rv && k + 2 < kend) ? q.z : 0.f; v[i][3] = (rv && k + 3 < kend) ? q.w : 0.f;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < R / 32; ++i) {
-            const int r = row0 + (t >> 3) + 32 * i;
-            const float* p = base + (long)min(r, nrows - 1) * ld;
-            float q[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) q[j] = p[min(k + j, kend - 1)];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[i][j] = (r < nrows && k + j < kend) ? q[j] : 0.f;
-        }
-    }
-}
-// "RC": the row (m or n) index is contiguous: X(r,k) = base[k*ld + r].
-// R = 128: thread t loads k = (t&7)*4 + i (i < 4), row-quad (t>>3); v[i][j] = X(row0 + 4*(t>>3) + j, k).
-// R =  64: row-quad (t>>3)&15, k = (t&7)*4 + 2*(t>>7) + i (i < 2).
-template <int R, bool MASK>
-__device__ __forceinline__ void load_rc(const float* __restrict__ base, long ld, int row0, int nrows,
-                                        int k0, int kend, bool vec, float v[4][4]) {
-    const int t = threadIdx.x;
-    constexpr int NI = R / 32;
-    const int r = row0 + ((R == 128) ? (t >> 3) : ((t >> 3) & 15)) * 4;
-    const int kb = k0 + (t & 7) * 4 + ((R == 128) ? 0 : 2 * (t >> 7));
-    if (!MASK) {
-        const float* p0 = base + (long)kb * ld + r;
+    const int cq = min(c, (climit - 1) & ~3);
+    if (vec) {      // the branch on `vec` stands outside the row loop: the rows' loads issue back to back
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            const float4 q = *reinterpret_cast<const float4*>(p0 + (long)i * ld);
-            v[i][0] = q.x; v[i][1] = q.y; v[i][2] = q.z; v[i][3] = q.w;
-        }
-        return;
-    }
-    const int rq = min(r, (nrows - 1) & ~3);
-    if (vec) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int k = kb + i;
-            const float4 q = *reinterpret_cast<const float4*>(base + (long)min(k, kend - 1) * ld + rq);
-            const bool kv = k < kend;
-            v[i][0] = (kv && r + 0 < nrows) ? q.x : 0.f; v[i][1] = (kv && r + 1 < nrows) ? q.y : 0.f;
-            v[i][2] = (kv && r + 2 < nrows) ? q.z : 0.f; v[i][3] = (kv && r + 3 < nrows) ? q.w : 0.f;
+            const int s = s0() + STEP * i;
+            const float4 q = *reinterpret_cast<const float4*>(base + (long)min(s, slimit - 1) * ld + cq);
+            const bool sv = s < slimit;
+            v[i][0] = (sv && c + 0 < climit) ? q.x : 0.f; v[i][1] = (sv && c + 1 < climit) ? q.y : 0.f;
+            v[i][2] = (sv && c + 2 < climit) ? q.z : 0.f; v[i][3] = (sv && c + 3 < climit) ? q.w : 0.f;
         }
     } else {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            const int k = kb + i;
-            const float* p = base + (long)min(k, kend - 1) * ld;
+            const int s = s0() + STEP * i;
+            const float* p = base + (long)min(s, slimit - 1) * ld;
             float q[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) q[j] = p[min(r + j, nrows - 1)];
+            for (int j = 0; j < 4; ++j) q[j] = p[min(c + j, climit - 1)];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[i][j] = (k < kend && r + j < nrows) ? q[j] : 0.f;
+            for (int j = 0; j < 4; ++j) v[i][j] = (s < slimit && c + j < climit) ? q[j] : 0.f;
         }
     }
 }
-
-// bf16-stored A operand (same thread mapping; 8-B vector loads of 4 elements).
-__device__ __forceinline__ float bfbits(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-template <int R, bool MASK>
-__device__ __forceinline__ void load_kc_bf16(const unsigned short* __restrict__ base, long ld, int row0, int nrows,
-                                             int k0, int kend, bool vec, float v[4][4]) {
+// bf16-stored A operand: same mapping and rule, 8-B vector loads of 4 elements.  Here the branch on `vec` sits inside the row loop: no
+// product path uses this overload, and its code is kept instruction for instruction.
+template <bool KC, int R, bool MASK>
+__device__ __forceinline__ void load_tile(const unsigned short* __restrict__ base, long ld, int row0, int nrows, int k0, int kend, bool vec, float v[4][4]) {
     const int t = threadIdx.x;
-    const int k = k0 + (t & 7) * 4;
+    constexpr int NI = R / 32, STEP = KC ? 32 : 1;
+    const int c = KC ? k0 + (t & 7) * 4 : row0 + ((R == 128) ? (t >> 3) : ((t >> 3) & 15)) * 4;
+    const int sRC = KC ? 0 : k0 + (t & 7) * 4 + ((R == 128) ? 0 : 2 * (t >> 7));
+    auto s0 = [&]() { return KC ? row0 + (t >> 3) : sRC; };
+    const int climit = KC ? kend : nrows, slimit = KC ? nrows : kend;
     if (!MASK) {
-        const unsigned short* p0 = base + (long)(row0 + (t >> 3)) * ld + k;
+        const unsigned short* p0 = base + (long)s0() * ld + c;
 #pragma unroll
-        for (int i = 0; i < R / 32; ++i) {
-            const uint2 u = *reinterpret_cast<const uint2*>(p0 + (long)(32 * i) * ld);
+        for (int i = 0; i < NI; ++i) {
+            const uint2 u = *reinterpret_cast<const uint2*>(p0 + (long)(STEP * i) * ld);
             v[i][0] = __uint_as_float(u.x << 16); v[i][1] = __uint_as_float(u.x & 0xffff0000u);
             v[i][2] = __uint_as_float(u.y << 16); v[i][3] = __uint_as_float(u.y & 0xffff0000u);
         }
         return;
     }
-    const int kq = min(k, (kend - 1) & ~3);
+    const int cq = min(c, (climit - 1) & ~3);
 #pragma unroll
-    for (int i = 0; i < R / 32; ++i) {
-        const int r = row0 + (t >> 3) + 32 * i;
-        const unsigned short* p = base + (long)min(r, nrows - 1) * ld;
+    for (int i = 0; i < NI; ++i) {
+        const int s = s0() + STEP * i;
+        const unsigned short* p = base + (long)min(s, slimit - 1) * ld;
         unsigned short q[4];
         if (vec) {
-            const uint2 u = *reinterpret_cast<const uint2*>(p + kq);
+            const uint2 u = *reinterpret_cast<const uint2*>(p + cq);
             q[0] = u.x & 0xffff; q[1] = u.x >> 16; q[2] = u.y & 0xffff; q[3] = u.y >> 16;
         } else {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) q[j] = p[min(k + j, kend - 1)];
+            for (int j = 0; j < 4; ++j) q[j] = p[min(c + j, climit - 1)];
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[i][j] = (r < nrows && k + j < kend) ? bfbits(q[j]) : 0.f;
-    }
-}
-template <int R, bool MASK>
-__device__ __forceinline__ void load_rc_bf16(const unsigned short* __restrict__ base, long ld, int row0, int nrows,
-                                             int k0, int kend, bool vec, float v[4][4]) {
-    const int t = threadIdx.x;
-    const int r = row0 + ((R == 128) ? (t >> 3) : ((t >> 3) & 15)) * 4;
-    const int kb = k0 + (t & 7) * 4 + ((R == 128) ? 0 : 2 * (t >> 7));
-    if (!MASK) {
-        const unsigned short* p0 = base + (long)kb * ld + r;
-#pragma unroll
-        for (int i = 0; i < R / 32; ++i) {
-            const uint2 u = *reinterpret_cast<const uint2*>(p0 + (long)i * ld);
-            v[i][0] = __uint_as_float(u.x << 16); v[i][1] = __uint_as_float(u.x & 0xffff0000u);
-            v[i][2] = __uint_as_float(u.y << 16); v[i][3] = __uint_as_float(u.y & 0xffff0000u);
-        }
-        return;
-    }
-    const int rq = min(r, (nrows - 1) & ~3);
-#pragma unroll
-    for (int i = 0; i < R / 32; ++i) {
-        const int k = kb + i;
-        const unsigned short* p = base + (long)min(k, kend - 1) * ld;
-        unsigned short q[4];
-        if (vec) {
-            const uint2 u = *reinterpret_cast<const uint2*>(p + rq);
-            q[0] = u.x & 0xffff; q[1] = u.x >> 16; q[2] = u.y & 0xffff; q[3] = u.y >> 16;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) q[j] = p[min(r + j, nrows - 1)];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[i][j] = (k < kend && r + j < nrows) ? bfbits(q[j]) : 0.f;
+        for (int j = 0; j < 4; ++j) v[i][j] = (s < slimit && c + j < climit) ? spe_bf2f(q[j]) : 0.f;
     }
 }
 
 // ---- registers -> LDS (bf16 via v_cvt_pk_bf16_f32, optionally hi/lo split) -------------------
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-template <bool SPLIT>
-__device__ __forceinline__ void store4(unsigned short* hi, unsigned short* lo, int off,
-                                       float a, float b, float c, float d) {
-    bf16x4_t h;
-    h[0] = (__bf16)a; h[1] = (__bf16)b; h[2] = (__bf16)c; h[3] = (__bf16)d;
-    *reinterpret_cast<bf16x4_t*>(hi + off) = h;
+template <int N, bool SPLIT>
+__device__ __forceinline__ void store_bf16(unsigned short* hi, unsigned short* lo, int off, const float (&x)[N]) {
+    typedef __bf16 bf16xN_t __attribute__((ext_vector_type(N)));
+    bf16xN_t h, l;
+#pragma unroll
+    for (int k = 0; k < N; ++k) h[k] = (__bf16)x[k];
+    *reinterpret_cast<bf16xN_t*>(hi + off) = h;
     if (SPLIT) {
-        bf16x4_t l;
-        l[0] = (__bf16)(a - (float)h[0]); l[1] = (__bf16)(b - (float)h[1]);
-        l[2] = (__bf16)(c - (float)h[2]); l[3] = (__bf16)(d - (float)h[3]);
-        *reinterpret_cast<bf16x4_t*>(lo + off) = l;
+#pragma unroll
+        for (int k = 0; k < N; ++k) l[k] = (__bf16)(x[k] - (float)h[k]);
+        *reinterpret_cast<bf16xN_t*>(lo + off) = l;
     }
 }
 template <int R, bool SPLIT>
 __device__ __forceinline__ void stage_kc(unsigned short* hi, unsigned short* lo, const float v[4][4]) {
     const int t = threadIdx.x;
 #pragma unroll
-    for (int i = 0; i < R / 32; ++i)
-        store4<SPLIT>(hi, lo, ((t >> 3) + 32 * i) * LDSLD + (t & 7) * 4, v[i][0], v[i][1], v[i][2], v[i][3]);
-}
-template <bool SPLIT>
-__device__ __forceinline__ void store2(unsigned short* hi, unsigned short* lo, int off, float a, float b) {
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    bf16x2_t h;
-    h[0] = (__bf16)a; h[1] = (__bf16)b;
-    *reinterpret_cast<bf16x2_t*>(hi + off) = h;
-    if (SPLIT) {
-        bf16x2_t l;
-        l[0] = (__bf16)(a - (float)h[0]); l[1] = (__bf16)(b - (float)h[1]);
-        *reinterpret_cast<bf16x2_t*>(lo + off) = l;
-    }
+    for (int i = 0; i < R / 32; ++i) store_bf16<4, SPLIT>(hi, lo, ((t >> 3) + 32 * i) * LDSLD + (t & 7) * 4, v[i]);
 }
 template <int R, bool SPLIT>
 __device__ __forceinline__ void stage_rc(unsigned short* hi, unsigned short* lo, const float v[4][4]) {
     const int t = threadIdx.x;
-    if (R == 128) {
+    constexpr int NI = R / 32;       // the NI quads of a thread are consecutive k: row j takes element j of each
+    const int off = ((R == 128) ? (t >> 3) : ((t >> 3) & 15)) * 4 * LDSLD + (t & 7) * 4 + ((R == 128) ? 0 : 2 * (t >> 7));
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            store4<SPLIT>(hi, lo, ((t >> 3) * 4 + j) * LDSLD + (t & 7) * 4, v[0][j], v[1][j], v[2][j], v[3][j]);
-    } else {
+    for (int j = 0; j < 4; ++j) {
+        float x[NI];
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            store2<SPLIT>(hi, lo, (((t >> 3) & 15) * 4 + j) * LDSLD + (t & 7) * 4 + 2 * (t >> 7), v[0][j], v[1][j]);
+        for (int i = 0; i < NI; ++i) x[i] = v[i][j];
+        store_bf16<NI, SPLIT>(hi, lo, off + j * LDSLD, x);
     }
 }
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + spe_erff(x * 0.70710678118654752f)); }
 
 // TA: opA(m,k) = A[k*lda+m] (else A[m*lda+k]).  TB: opB(k,n) = B[n*ldb+k] (else B[k*ldb+n]).
 template <int T, bool TA, bool TB, bool SPLIT>
@@ -284,21 +211,23 @@ __global__ __launch_bounds__(256) void spe_gemm_kernel(GemmArgs p) {
     auto gload = [&](int kt) {
         const int k0 = kt * BK;
         const bool k_in = k0 + BK <= p.K;
-        if (rowsA_in && k_in) {
-            if (p.a_bf16) { if (TA) load_rc_bf16<T, false>(A16, p.lda, m0, p.M, k0, p.K, true, va); else load_kc_bf16<T, false>(A16, p.lda, m0, p.M, k0, p.K, true, va); }
-            else          { if (TA) load_rc<T, false>(A, p.lda, m0, p.M, k0, p.K, true, va); else load_kc<T, false>(A, p.lda, m0, p.M, k0, p.K, true, va); }
-        } else {
-            if (p.a_bf16) { if (TA) load_rc_bf16<T, true>(A16, p.lda, m0, p.M, k0, p.K, p.vecA, va); else load_kc_bf16<T, true>(A16, p.lda, m0, p.M, k0, p.K, p.vecA, va); }
-            else          { if (TA) load_rc<T, true>(A, p.lda, m0, p.M, k0, p.K, p.vecA, va); else load_kc<T, true>(A, p.lda, m0, p.M, k0, p.K, p.vecA, va); }
-        }
-        if (rowsB_in && k_in) { if (TB) load_kc<T, false>(B, p.ldb, n0, p.N, k0, p.K, true, vb); else load_rc<T, false>(B, p.ldb, n0, p.N, k0, p.K, true, vb); }
-        else                  { if (TB) load_kc<T, true>(B, p.ldb, n0, p.N, k0, p.K, p.vecB, vb); else load_rc<T, true>(B, p.ldb, n0, p.N, k0, p.K, p.vecB, vb); }
+        auto loadA = [&](auto MASK, bool vec) {      // interior / masked is the outer choice, the element type the inner one, for A as for B
+            if (p.a_bf16) load_tile<!TA, T, MASK()>(A16, p.lda, m0, p.M, k0, p.K, vec, va);
+            else          load_tile<!TA, T, MASK()>(A, p.lda, m0, p.M, k0, p.K, vec, va);
+        };
+        if (rowsA_in && k_in) loadA(std::false_type(), true); else loadA(std::true_type(), p.vecA);
+        if (rowsB_in && k_in) load_tile<TB, T, false>(B, p.ldb, n0, p.N, k0, p.K, true, vb);
+        else                  load_tile<TB, T, true>(B, p.ldb, n0, p.N, k0, p.K, p.vecB, vb);
     };
     auto stage = [&](int buf) {
         if (TA) stage_rc<T, SPLIT>(sA(buf, 0), sA(buf, NPL - 1), va); else stage_kc<T, SPLIT>(sA(buf, 0), sA(buf, NPL - 1), va);
         if (TB) stage_kc<T, SPLIT>(sB(buf, 0), sB(buf, NPL - 1), vb); else stage_rc<T, SPLIT>(sB(buf, 0), sB(buf, NPL - 1), vb);
     };
 
+    // one MFMA operand fragment: lane (fr, fk) reads 8 consecutive k of row `row` of an LDS plane
+    auto frag = [&](const unsigned short* plane, int row) {
+        return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u16x8_t*>(plane + row * LDSLD + fk));
+    };
     if (nt > 0) {
         gload(kt_begin);
         stage(0);
@@ -309,10 +238,10 @@ __global__ __launch_bounds__(256) void spe_gemm_kernel(GemmArgs p) {
             bf16x8_t a[NF], b[NF];
 #pragma unroll
             for (int i = 0; i < NF; ++i)
-                a[i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u16x8_t*>(sA(buf, 0) + (wm * WT + i * 16 + fr) * LDSLD + fk));
+                a[i] = frag(sA(buf, 0), wm * WT + i * 16 + fr);
 #pragma unroll
             for (int j = 0; j < NF; ++j)
-                b[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u16x8_t*>(sB(buf, 0) + (wn * WT + j * 16 + fr) * LDSLD + fk));
+                b[j] = frag(sB(buf, 0), wn * WT + j * 16 + fr);
 #pragma unroll
             for (int i = 0; i < NF; ++i)
 #pragma unroll
@@ -322,10 +251,10 @@ __global__ __launch_bounds__(256) void spe_gemm_kernel(GemmArgs p) {
                 bf16x8_t al[NF], bl[NF];
 #pragma unroll
                 for (int i = 0; i < NF; ++i)
-                    al[i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u16x8_t*>(sA(buf, 1) + (wm * WT + i * 16 + fr) * LDSLD + fk));
+                    al[i] = frag(sA(buf, 1), wm * WT + i * 16 + fr);
 #pragma unroll
                 for (int j = 0; j < NF; ++j)
-                    bl[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u16x8_t*>(sB(buf, 1) + (wn * WT + j * 16 + fr) * LDSLD + fk));
+                    bl[j] = frag(sB(buf, 1), wn * WT + j * 16 + fr);
 #pragma unroll
                 for (int i = 0; i < NF; ++i)
 #pragma unroll
@@ -389,7 +318,7 @@ __global__ __launch_bounds__(256) void spe_gemm_kernel(GemmArgs p) {
                 for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
             } else if (p.act == 2) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+                for (int r = 0; r < 4; ++r) v[r] = spe_gelu_erf(v[r]);
             }
             if (full) *reinterpret_cast<float4*>(C + off) = make_float4(v[0], v[1], v[2], v[3]);
             else {
@@ -446,8 +375,16 @@ static int gemm_f32_select(int M, int N, int K, long lda, long ldb, long ldc, in
     return 0;
 }
 
+// ---- the instances that exist: X(T, TA, TB, SPLIT).  gemm_f32_select names nothing else (it refuses TA && TB); the launcher's switch is
+// generated from this list.
+#define F32_GEMM_INSTANCES(X)                                                                                       \
+    X(64, false, true, false)  X(64, false, true, true)  X(64, false, false, false)  X(64, false, false, true)      \
+    X(64, true, false, false)  X(64, true, false, true)  X(128, false, true, false)  X(128, false, true, true)      \
+    X(128, false, false, false) X(128, false, false, true) X(128, true, false, false) X(128, true, false, true)
+constexpr int f32_gemm_key(int T, int TA, int TB, int SPLIT) { return ((T * 2 + TA) * 2 + TB) * 2 + SPLIT; }
+
 template <int T, bool TA, bool TB, bool SPLIT>
-static int launch_gemm_t(const GemmArgs& p, int grid_x, int nbatch, hipStream_t stream) {
+static int launch_gemm(const GemmArgs& p, int grid_x, int nbatch, hipStream_t stream) {
     constexpr int smem = 2 * 2 * (SPLIT ? 2 : 1) * T * LDSLD * (int)sizeof(unsigned short);
     static bool attr_set = false;
     if (!attr_set) {
@@ -460,12 +397,6 @@ static int launch_gemm_t(const GemmArgs& p, int grid_x, int nbatch, hipStream_t 
     hipLaunchKernelGGL((spe_gemm_kernel<T, TA, TB, SPLIT>), grid, dim3(256), smem, stream, p);
     SPE_CHECK_LAUNCH();
     return 0;
-}
-
-template <bool TA, bool TB, bool SPLIT>
-static int launch_gemm(const GemmArgs& p, const GemmPlan& s, int nbatch, hipStream_t stream) {
-    if (s.T == 128) return launch_gemm_t<128, TA, TB, SPLIT>(p, s.grid, nbatch, stream);
-    return launch_gemm_t<64, TA, TB, SPLIT>(p, s.grid, nbatch, stream);
 }
 
 // C-ABI: see include/spe_hip.h (spe_gemm_f32_plan).  Host only: the selection for a problem, no device needed.
@@ -482,21 +413,7 @@ extern "C" int spe_gemm_f32_plan(int M, int N, int K, long lda, long ldb, long l
     return 0;
 }
 
-extern "C" int spe_gemm_ex(const void* A, int a_bf16, const float* B, float* C, const float* bias, float* C2,
-                           int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB,
-                           int batch0, int batch1, long sA0, long sA1, long sB0, long sB1, long sC0, long sC1,
-                           float alpha, int act, int splitk, int precision, hipStream_t stream);
-
-// C-ABI: see include/spe_hip.h (spe_gemm_f32).
-extern "C" int spe_gemm_f32(const float* A, const float* B, float* C, const float* bias, float* C2,
-                            int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB,
-                            int batch0, int batch1, long sA0, long sA1, long sB0, long sB1, long sC0, long sC1,
-                            float alpha, int act, int splitk, int precision, hipStream_t stream) {
-    return spe_gemm_ex(A, 0, B, C, bias, C2, M, N, K, lda, ldb, ldc, transA, transB, batch0, batch1, sA0, sA1, sB0, sB1, sC0, sC1,
-                       alpha, act, splitk, precision, stream);
-}
-
-// Same contraction with the A operand optionally stored as bf16 (a_bf16 = 1; lda / sA* in elements).
+// C-ABI: see include/spe_hip.h (spe_gemm_ex): the contraction with the A operand optionally stored as bf16 (a_bf16 = 1; lda / sA* in elements).
 extern "C" int spe_gemm_ex(const void* A, int a_bf16, const float* B, float* C, const float* bias, float* C2,
                            int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB,
                            int batch0, int batch1, long sA0, long sA1, long sB0, long sB1, long sC0, long sC1,
@@ -513,8 +430,20 @@ extern "C" int spe_gemm_ex(const void* A, int a_bf16, const float* B, float* C, 
     p.alpha = alpha; p.act = act; p.slab = s.slab;
     p.kt_per_split = s.kt_per_split; p.splitk = s.splitk;
     p.vecA = s.vecA; p.vecB = s.vecB; p.xcd_bind = s.xcd_bind;
-    const int nbatch = batch0 * batch1;
-    if (!s.TA && s.TB)  return s.SPLIT ? launch_gemm<false, true, true>(p, s, nbatch, stream) : launch_gemm<false, true, false>(p, s, nbatch, stream);
-    if (!s.TA && !s.TB) return s.SPLIT ? launch_gemm<false, false, true>(p, s, nbatch, stream) : launch_gemm<false, false, false>(p, s, nbatch, stream);
-    return s.SPLIT ? launch_gemm<true, false, true>(p, s, nbatch, stream) : launch_gemm<true, false, false>(p, s, nbatch, stream);
+    switch (f32_gemm_key(s.T, s.TA, s.TB, s.SPLIT)) {
+#define F32_GEMM_CASE(T, TA, TB, SPLIT) \
+    case f32_gemm_key(T, TA, TB, SPLIT): return launch_gemm<T, TA, TB, SPLIT>(p, s.grid, batch0 * batch1, stream);
+        F32_GEMM_INSTANCES(F32_GEMM_CASE)
+#undef F32_GEMM_CASE
+    }
+    return -2;          // unreachable while gemm_f32_select names members of the list (tests/test_f32_gemm_plan_cpu.py)
+}
+
+// C-ABI: see include/spe_hip.h (spe_gemm_f32).
+extern "C" int spe_gemm_f32(const float* A, const float* B, float* C, const float* bias, float* C2,
+                            int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB,
+                            int batch0, int batch1, long sA0, long sA1, long sB0, long sB1, long sC0, long sC1,
+                            float alpha, int act, int splitk, int precision, hipStream_t stream) {
+    return spe_gemm_ex(A, 0, B, C, bias, C2, M, N, K, lda, ldb, ldc, transA, transB, batch0, batch1, sA0, sA1, sB0, sB1, sC0, sC1,
+                       alpha, act, splitk, precision, stream);
 }

@@ -54,8 +54,6 @@ __device__ __forceinline__ float4 ep_h2f4(uint2 u) {
     const ep_h4_t h = __builtin_bit_cast(ep_h4_t, u);
     return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
 }
-__device__ __forceinline__ float gelu_erf16(float x) { return 0.5f * x * (1.0f + spe_erff(x * 0.70710678118654752f)); }
-
 
 // ---- extended epilogue.  v = alpha*acc + bias ; C2 = v ; v = act(v) or v * act'(aux) ; C = v (optional);
 // the bf16 copies go through LDS (smem16: the operand buffers, free by now; the caller has synchronised the workgroup) so that both
@@ -167,7 +165,7 @@ __device__ __forceinline__ void gemm16_epilogue_ex(const Gemm16Args& p, f32x4_t 
                 for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
             } else if (p.act == 2) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = gelu_erf16(v[r]);
+                for (int r = 0; r < 4; ++r) v[r] = spe_gelu_erf(v[r]);
             }
             if (p.drop_p > 0.f) {                     // same mask as spe_dropout on the [M, N] result (n % 4 == 0: one Philox call)
                 float ks[4];
@@ -314,7 +312,7 @@ __device__ __forceinline__ void gemm16_epilogue_plain(const Gemm16Args& p, f32x4
                     for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
                 } else if (p.act == 2) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = gelu_erf16(v[r]);
+                    for (int r = 0; r < 4; ++r) v[r] = spe_gelu_erf(v[r]);
                 }
             }
             if (p.h16 & 2) {        // fp16 output (saturating, NaN kept): the consumer packs these values into fp16 MFMA operands anyway
