@@ -42,7 +42,7 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_resample_plan / _tables / _h / _v (the input transforms: Pillow-exact bilinear resize, crop, flip, normalise, pad),
  * spe_ledger_state_bytes / _record / _total_bwd / _summary (the step ledger: weighted total, loss meters and non-finite guard on the device)
  * spe_gemm_f32_plan (the kernel selection and launch choices of spe_gemm_f32 / spe_gemm_ex, host only)
- * - 100 entry points */
+ * - 100 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -526,10 +526,10 @@ int spe_colsum_bf16_blocks(const void* x, long ld, long R, int nblk, int blkC, f
  * keep flags in keepbits (B*H*ntq*ntk*4 64-bit words, needed when p_drop > 0) and the backward reads them.
  * spe_mha_plan: number of key chunks the forward / dQ kernels split the keys into (few query tiles -> many chunks).
  * spe_mha_fwd: Opart [B*H*ntq*nch][ceil(dv/16)][64][4] and ML [B*H*ntq*nch][16][2] floats of workspace ->
- *   O [B,Lq,H*dv], LSE [B,H,Lq] (log2 domain).  spe_mha_bwd: D [B,H,Lq] = rowsum(dO.O); dq [B,Lq,H,dk] must be
- *   zero-initialised when nch > 1 and dq_ws == NULL (atomic accumulation over chunks); with dq_ws [nch][B*Lq*H*dk] every
- *   chunk writes its own partial slab instead (sum them with spe_colsum: no atomics, fixed order) and dq is not touched;
- *   dk [B,Lk,H,dk], dv [B,Lk,H,dv] are overwritten. */
+ *   O [B,Lq,H*dv], LSE [B,H,Lq] (log2 domain).  spe_mha_bwd: D [B,H,Lq] = rowsum(dO.O); with one key chunk dq [B,Lq,H,dk]
+ *   is overwritten (no zero-initialising) and dq_ws is not read; with nch > 1 every chunk writes its own partial slab of
+ *   dq_ws [nch][B*Lq*H*dk] (sum them with spe_colsum: no atomics, fixed order), dq is not touched, and dq_ws == NULL is
+ *   refused with -2, nothing launched; dk [B,Lk,H,dk], dv [B,Lk,H,dv] are overwritten. */
 int spe_mha_plan(int B, int H, int Lq, int Lk, int* nch);
 int spe_mha_fwd(const void* Qf, const void* Kf, const void* V16, const void* mask, float* Opart, float* ML, float* O,
                 float* LSE, void* keepbits, int B, int H, int Lq, int Lk, int dk, int dv, int nch, float p_drop,

@@ -929,6 +929,16 @@ class _Attention(Function):
         return dq, dk_, dv_, None, None, None, None
 
 
+def _mha_flash_bwd(dO, O, lse, Qf, Kf, Vf, K16, Q16, mask_u8, keep, meta):
+    """The backward of both flash nodes: D = rowsum(dO . O), the two fragment packs of dO, spe_mha_bwd.
+    meta = (B, Lq, Lk, H, dk, dv, nch, scale, p_drop) -> dq [B,Lq,H,dk], dk [B,Lk,H,dk], dv [B,Lk,H,dv] fp32."""
+    B, Lq, Lk, H, dk, dv, nch, scale, p_drop = meta
+    dO4 = dO.contiguous().view(B, Lq, H, dv)
+    D = K.rowdot(dO4, O.contiguous().view(B, Lq, H, dv))                                 # [B,H,Lq]
+    dOf, dO16 = K.attn_pack_multi([(dO4, 1.0, 322), (dO4, 1.0, 16)])
+    return K.mha_bwd(Qf, Kf, Vf, dOf, K16, Q16, dO16, mask_u8, lse, D, keep, B, H, Lq, Lk, dk, dv, nch, scale, p_drop)
+
+
 class _AttentionFlash(Function):
     """Same operator without the [B,H,Lq,Lk] tensors (csrc/mha_flash.hip): online-softmax forward, two-kernel backward.
     Used in bf16 mode when no attention map is requested and the head dims fit (q/k <= 96, v <= 64)."""
@@ -959,12 +969,7 @@ class _AttentionFlash(Function):
     @K.backward_scope
     def backward(ctx, dO):
         Qf, Kf, Q16, K16, Vf, O, lse, mask_u8, keep = ctx.saved_tensors
-        B, Lq, Lk, H, dk, dv, nch, scale, p_drop = ctx.meta
-        dO = dO.contiguous()
-        dO4 = dO.view(B, Lq, H, dv)
-        D = K.rowdot(dO4, O.contiguous().view(B, Lq, H, dv))                             # [B,H,Lq] = rowsum(dO . O)
-        dOf, dO16 = K.attn_pack_multi([(dO4, 1.0, 322), (dO4, 1.0, 16)])
-        dq, dk_, dv_ = K.mha_bwd(Qf, Kf, Vf, dOf, K16, Q16, dO16, mask_u8, lse, D, keep, B, H, Lq, Lk, dk, dv, nch, scale, p_drop)
+        dq, dk_, dv_ = _mha_flash_bwd(dO, O, lse, Qf, Kf, Vf, K16, Q16, mask_u8, keep, ctx.meta)
         return dq, dk_, dv_, None, None, None
 
 
@@ -1094,12 +1099,7 @@ class _CrossAttentionKV(Function):
         h = ctx.holder
         L = h.dims[0]
         d = H * dh
-        dO = dO.contiguous()
-        dO4 = dO.view(B, Lq, H, dh)
-        D = K.rowdot(dO4, O.contiguous().view(B, Lq, H, dh))                             # [B,H,Lq] = rowsum(dO . O)
-        dOf, dO16 = K.attn_pack_multi([(dO4, 1.0, 322), (dO4, 1.0, 16)])
-        dq, dk_, dv_ = K.mha_bwd(Qf, h.Kf[layer], h.Vf[layer], dOf, h.K16[layer], Q16, dO16, mask_u8, lse, D, keep, B, H, Lq, S, dk, dh, nch,
-                                 scale, p_drop)
+        dq, dk_, dv_ = _mha_flash_bwd(dO, O, lse, Qf, h.Kf[layer], h.Vf[layer], h.K16[layer], Q16, mask_u8, keep, ctx.meta[:9])
         if not ctx.needs_input_grad[1]:                 # the memory side takes no gradient (frozen projections, detached memory): nothing to scatter
             return dq, None, None, None, None, None, None
         if h.dYm is None:

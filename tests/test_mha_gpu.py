@@ -447,3 +447,31 @@ def test_refusals_launch_nothing(dev):
     r = dict(O=R.ratio(O3, ref["O"], ref["bO"]), LSE=R.ratio(lse3, ref["LSE"], ref["bLSE"]))
     assert ok and r["O"] <= 2.0 and r["LSE"] <= 2.0, r
     print("MHAEDGE refusals dk=97:-2 dv=65:-2 p>0-without-words:-2 nch-not-a-chunking:-5 empty:0-untouched nch=3-of-9-tiles", r)
+
+
+def test_bwd_refuses_chunks_without_slabs(dev):
+    """spe_mha_bwd: -2 and nothing launched for more than one key chunk without dq slabs (chunks never add into one dq); one chunk
+    without slabs is accepted and overwrites dq directly."""
+    from spe_amd import kernels as K
+    from spe_amd import lib
+    B, H, Lq, Lk, dk, dv = 1, 2, 17, 144, 32, 16
+    case = (B, H, Lq, Lk, dk, dv, "none", "normal", 0, 2)
+    op, fr, mask_u8, keep, ref = _prep(case, dev)
+    lse, D = _lse_d(ref)
+    n_q, n_k, n_v = B * Lq * H * dk, B * Lk * H * dk, B * Lk * H * dv
+    dq, dk_, dv_ = _nan(n_q + SPARE, dev), _nan(n_k + SPARE, dev), _nan(n_v + SPARE, dev)
+
+    def call(nch):
+        K._call("spe_mha_bwd", K._p(fr["Qf"]), K._p(fr["Kf"]), K._p(fr["Vf"]), K._p(fr["dOf"]), K._p(fr["K16"]), K._p(fr["Q16"]),
+                K._p(fr["dO16"]), None, K._p(lse), K._p(D), None, K._p(dq), None, K._p(dk_), K._p(dv_), B, H, Lq, Lk, dk, dv, nch,
+                float(op["scale"]), 0.0, K._st())
+        torch.cuda.synchronize()
+
+    with pytest.raises(lib.SpeLibraryError, match="status -2$"):
+        call(2)
+    assert all(bool(torch.isnan(b).all()) for b in (dq, dk_, dv_))
+    call(1)
+    assert all(bool(torch.isfinite(b[:n]).all()) and _untouched(b, n) for b, n in ((dq, n_q), (dk_, n_k), (dv_, n_v)))
+    r = R.ratio(dq[:n_q].view(B, Lq, H, dk), ref["dq"], ref["bdq"])
+    print("MHAEDGE bwd-refusal nch=2-without-slabs:-2-untouched nch=1-without-slabs:dq-direct dq=%.3f" % r)
+    assert r <= 2.0, r

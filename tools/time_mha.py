@@ -6,7 +6,7 @@ from spe_amd import kernels as K, ops
 dev = torch.device("cuda:0")
 
 
-def t(fn, n=5):
+def t(fn, n=200):
     fn(); torch.cuda.synchronize()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
