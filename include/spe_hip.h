@@ -749,6 +749,32 @@ int spe_adamw_flat(float* p, float* g, float* m, float* v, long n, const long* s
                    const float* partials, int npartials, float max_norm, int write_grad, float grad_scale,
                    spe_stream_t stream);
 
+/* ---- the same step, skipped on the device when the reduced gradient is not finite (reference engine.py:147-159 exits before
+ * optimizer.step() on a non-finite loss; here the decision sits where the norm already is, no host read).  Per optimizer step:
+ * spe_sqnorm_partials for every bucket, ONE spe_adamw_gate, then spe_adamw_flat_guarded per bucket.
+ * The guard block: SPE_ADAMW_GUARD_WORDS 4-byte words, 16-B aligned, zeroed by the caller before the first step.
+ *   int32 [0] applied steps   [1] skipped steps   [2] 1-based attempt index (applied + skipped) of the first skipped step, 0: none
+ *         [3] apply: this step's decision (1 / 0)
+ *   fp32  [4] clip * grad_scale of this step (0 when skipped)   [5] 1 - beta1^t   [6] sqrt(1 - beta2^t)   [7] the gradient norm
+ *         grad_scale * sqrt(sum partials) (inf / NaN when skipped)   [8] applied steps as a float (torch's `step` entry)
+ *   words 9 .. 15 are reserved and never written.
+ * spe_adamw_gate (one workgroup): sums partials[0 .. npartials) - the partials of ALL buckets - with the reduction spe_adamw_flat
+ * uses, so clip = min(1, max_norm / (norm + 1e-6)) has the bits of the unguarded path (max_norm <= 0: no clipping; the sum is
+ * taken all the same).  apply = isfinite(sum): a NaN or an infinity anywhere in the buckets skips the step, and so does a squared
+ * norm that overflows fp32 (an element beyond ~1.8e19 is enough).  t is the APPLIED count including this step - a skipped step
+ * does not shift the bias corrections of later ones; beta^t is taken in fp64 and rounded to fp32 once.  One lane writes the block
+ * with ordinary stores.  -2: guard NULL or misaligned, partials NULL, npartials < 1.
+ * spe_adamw_flat_guarded: spe_adamw_flat with the block in place of bias_c1, bias_c2, partials, max_norm and grad_scale.  Every
+ * workgroup reads the record; with apply == 0 it returns before its first store (p, g, m, v keep their bits, whatever
+ * write_grad says), otherwise the per-element arithmetic is spe_adamw_flat's (one kernel body).  Status as spe_adamw_flat: -2
+ * for misaligned buffers (the block included) or nseg outside 1..64, 0 and no launch for n <= 0. */
+#define SPE_ADAMW_GUARD_WORDS 16
+int spe_adamw_gate(void* guard, const float* partials, int npartials, float max_norm, float grad_scale, double beta1,
+                   double beta2, spe_stream_t stream);
+int spe_adamw_flat_guarded(float* p, float* g, float* m, float* v, long n, const long* seg_end, const float* seg_lr,
+                           const float* seg_wd, int nseg, float beta1, float beta2, float eps, const void* guard,
+                           int write_grad, spe_stream_t stream);
+
 /* ---- gradient accumulation beside the flat buckets (reference engine.py:161-165 together with main.py:170-172: ONE
  * optimizer step over world x batch images; on fewer GPUs the missing ranks become micro-steps, spe_amd/dp.py accum_steps).
  * dst[i] = a[i] + b[i]; b == NULL: the bit copy dst[i] = a[i] (-0.0 and NaN payloads survive).  dst may alias a or b.

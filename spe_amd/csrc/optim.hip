@@ -72,26 +72,89 @@ struct AdamwArgs {
     const long* seg_end; const float* seg_lr; const float* seg_wd; int nseg;
     float beta1, beta2, eps, bc1, bc2sqrt;
     const float* partials; int npartials; float max_norm; int write_grad; float gscale;
+    const int* guard;                  // GUARDED only: the guard block, in place of bc1, bc2sqrt, partials, max_norm and gscale
 };
+
+// Sum of the squared-norm partials of ALL buckets: lane-strided, then spe_block_sum.  The one reduction behind the clip factor of the
+// unguarded update (every workgroup's prologue) and behind the gate's decision, so both paths clip by the same bits.
+__device__ __forceinline__ float adamw_sqnorm_total(const float* partials, int npartials, float* red) {
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < npartials; i += 256) acc += partials[i];
+    return spe_block_sum(acc, red);
+}
+// norm of the scaled gradient and clip * gscale from that sum (max_norm <= 0: no clipping)
+__device__ __forceinline__ float adamw_clip_scale(float sqsum, float max_norm, float gscale, float* norm) {
+    const float tot = gscale * sqrtf(sqsum);
+    *norm = tot;
+    const float clip = max_norm > 0.f ? fminf(max_norm / (tot + 1e-6f), 1.f) : 1.f;
+    return clip * gscale;
+}
+
+// Guard block words (include/spe_hip.h, SPE_ADAMW_GUARD_*)
+enum { GW_APPLIED = 0, GW_SKIPPED = 1, GW_FIRST = 2, GW_APPLY = 3, GW_CLIP = 4, GW_BC1 = 5, GW_BC2SQRT = 6, GW_NORM = 7, GW_STEP_F = 8 };
+
+// One workgroup per optimizer step, after the spe_sqnorm_partials launches of every bucket: the decision and the step's constants.
+// apply = isfinite(sum of squares) - a NaN or an infinity anywhere in the buckets, or a squared norm past FLT_MAX, skips the step.
+// The bias corrections follow the APPLIED count t (a skipped step must not shift the later ones): beta^t in fp64, rounded once.
+__global__ __launch_bounds__(256) void adamw_gate_kernel(int* guard, const float* __restrict__ partials, int npartials, float max_norm,
+                                                         float gscale, double beta1, double beta2) {
+    __shared__ float red[16];
+    const float sqsum = adamw_sqnorm_total(partials, npartials, red);
+    if (threadIdx.x != 0) return;
+    float norm;
+    const float cs = adamw_clip_scale(sqsum, max_norm, gscale, &norm);
+    const int apply = isfinite(sqsum) ? 1 : 0;
+    const int applied = guard[GW_APPLIED] + apply, skipped = guard[GW_SKIPPED] + 1 - apply;
+    const double t = (double)applied;
+    float* gf = reinterpret_cast<float*>(guard);
+    guard[GW_APPLIED] = applied;
+    guard[GW_SKIPPED] = skipped;
+    if (!apply && guard[GW_FIRST] == 0) guard[GW_FIRST] = applied + skipped;       // 1-based index of this attempt
+    guard[GW_APPLY] = apply;
+    gf[GW_CLIP] = apply ? cs : 0.f;
+    gf[GW_BC1] = (float)(1.0 - pow(beta1, t));
+    gf[GW_BC2SQRT] = (float)sqrt(1.0 - pow(beta2, t));
+    gf[GW_NORM] = norm;
+    gf[GW_STEP_F] = (float)applied;
+}
+
+// C-ABI: see include/spe_hip.h (spe_adamw_gate).
+extern "C" int spe_adamw_gate(void* guard, const float* partials, int npartials, float max_norm, float grad_scale, double beta1,
+                              double beta2, hipStream_t st) {
+    if (guard == nullptr || (reinterpret_cast<uintptr_t>(guard) & 15) || partials == nullptr || npartials < 1) return -2;
+    hipLaunchKernelGGL(adamw_gate_kernel, dim3(1), dim3(256), 0, st, static_cast<int*>(guard), partials, npartials, max_norm, grad_scale,
+                       beta1, beta2);
+    SPE_CHECK_LAUNCH();
+    return 0;
+}
 
 // torch.optim.AdamW (amsgrad = False, maximize = False):
 //   p *= 1 - lr*wd ; m = lerp(m, g, 1-beta1) ; v = beta2*v + (1-beta2) g^2 ;
 //   p -= (lr / (1-beta1^t)) * m / (sqrt(v)/sqrt(1-beta2^t) + eps)
 // with g first scaled by clip = min(1, max_norm / (||g||_2 + 1e-6)) over ALL parameters (torch clip_grad_norm_).
 // Element i belongs to the segment s with seg_end[s-1] <= i < seg_end[s] (parameter group: lr, weight decay).
+// GUARDED (spe_adamw_flat_guarded): clip * gscale and the bias corrections come from the guard block the gate launch left, and a
+// workgroup that reads apply == 0 returns before its first store - p, m, v and g keep their bits.  Everything after the prologue is
+// the one body of both instantiations.
+template <bool GUARDED>
 __global__ __launch_bounds__(256) void adamw_flat_kernel(AdamwArgs a) {
     __shared__ float red[16];
     __shared__ long s_end[ADAMW_MAXSEG];
     __shared__ float s_lr[ADAMW_MAXSEG], s_wd[ADAMW_MAXSEG];
-    for (int i = threadIdx.x; i < a.nseg; i += 256) { s_end[i] = a.seg_end[i]; s_lr[i] = a.seg_lr[i]; s_wd[i] = a.seg_wd[i]; }
-    float clip = 1.f;
-    if (a.max_norm > 0.f) {
-        float acc = 0.f;
-        for (int i = threadIdx.x; i < a.npartials; i += 256) acc += a.partials[i];
-        const float tot = a.gscale * sqrtf(spe_block_sum(acc, red));
-        clip = fminf(a.max_norm / (tot + 1e-6f), 1.f);
+    float clip, bc1, bc2sqrt;
+    if (GUARDED) {                                       // the record in one round trip, ahead of the decision that waits for it
+        const float* gf = reinterpret_cast<const float*>(a.guard);
+        const int apply = a.guard[GW_APPLY];
+        clip = gf[GW_CLIP]; bc1 = gf[GW_BC1]; bc2sqrt = gf[GW_BC2SQRT];
+        if (apply == 0) return;                          // the same word for every lane: the whole workgroup leaves
     }
-    clip *= a.gscale;
+    for (int i = threadIdx.x; i < a.nseg; i += 256) { s_end[i] = a.seg_end[i]; s_lr[i] = a.seg_lr[i]; s_wd[i] = a.seg_wd[i]; }
+    if (!GUARDED) {
+        float norm;
+        const float sqsum = a.max_norm > 0.f ? adamw_sqnorm_total(a.partials, a.npartials, red) : 0.f;
+        clip = adamw_clip_scale(sqsum, a.max_norm, a.gscale, &norm);
+        bc1 = a.bc1; bc2sqrt = a.bc2sqrt;
+    }
     __syncthreads();
     // grid-stride over float4 chunks: the prologue above (segment table, clip factor from the norm partials) is paid once
     // per workgroup, not once per 1024 elements (26 K workgroups for the 27 M parameters of cfg2: 0.41 -> 0.2x ms)
@@ -121,8 +184,8 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(AdamwArgs a) {
         float p = pv[j] * (1.f - lr * wd);
         const float m = mv[j] + (g - mv[j]) * (1.f - a.beta1);
         const float v = a.beta2 * vv[j] + (1.f - a.beta2) * g * g;
-        const float denom = sqrtf(v) / a.bc2sqrt + a.eps;
-        p -= (lr / a.bc1) * (m / denom);
+        const float denom = sqrtf(v) / bc2sqrt + a.eps;
+        p -= (lr / bc1) * (m / denom);
         pv[j] = p; gv[j] = g; mv[j] = m; vv[j] = v;
     }
     if (full) {
@@ -138,20 +201,40 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(AdamwArgs a) {
     }
 }
 
+// The launch of both entries: status codes, grid (one workgroup per 1024 elements, 2048 at most) and the shared arguments.
+template <bool GUARDED>
+static int adamw_flat_launch(AdamwArgs a, hipStream_t st) {
+    if (a.n <= 0) return 0;
+    if (a.nseg < 1 || a.nseg > ADAMW_MAXSEG) return -2;
+    if ((reinterpret_cast<uintptr_t>(a.p) | reinterpret_cast<uintptr_t>(a.g) | reinterpret_cast<uintptr_t>(a.m) | reinterpret_cast<uintptr_t>(a.v)) & 15) return -2;
+    if (GUARDED && (a.guard == nullptr || (reinterpret_cast<uintptr_t>(a.guard) & 15))) return -2;
+    long nb = (a.n + 1023) / 1024; if (nb > 2048) nb = 2048;
+    hipLaunchKernelGGL(adamw_flat_kernel<GUARDED>, dim3((unsigned)nb), dim3(256), 0, st, a);
+    SPE_CHECK_LAUNCH();
+    return 0;
+}
+
 // C-ABI: see include/spe_hip.h (spe_adamw_flat).  All flat buffers 16-B aligned, n elements.
 extern "C" int spe_adamw_flat(float* p, float* g, float* m, float* v, long n, const long* seg_end, const float* seg_lr,
                               const float* seg_wd, int nseg, float beta1, float beta2, float eps, float bias_c1, float bias_c2,
                               const float* partials, int npartials, float max_norm, int write_grad, float grad_scale,
                               hipStream_t st) {
-    if (n <= 0) return 0;
-    if (nseg < 1 || nseg > ADAMW_MAXSEG) return -2;
-    if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) return -2;
     AdamwArgs a;
     a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.seg_end = seg_end; a.seg_lr = seg_lr; a.seg_wd = seg_wd; a.nseg = nseg;
     a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.bc1 = bias_c1; a.bc2sqrt = sqrtf(bias_c2);
     a.partials = partials; a.npartials = npartials; a.max_norm = max_norm; a.write_grad = write_grad; a.gscale = grad_scale;
-    long nb = (n + 1023) / 1024; if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(adamw_flat_kernel, dim3((unsigned)nb), dim3(256), 0, st, a);
-    SPE_CHECK_LAUNCH();
-    return 0;
+    a.guard = nullptr;
+    return adamw_flat_launch<false>(a, st);
+}
+
+// C-ABI: see include/spe_hip.h (spe_adamw_flat_guarded).
+extern "C" int spe_adamw_flat_guarded(float* p, float* g, float* m, float* v, long n, const long* seg_end, const float* seg_lr,
+                                      const float* seg_wd, int nseg, float beta1, float beta2, float eps, const void* guard,
+                                      int write_grad, hipStream_t st) {
+    AdamwArgs a;
+    a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.seg_end = seg_end; a.seg_lr = seg_lr; a.seg_wd = seg_wd; a.nseg = nseg;
+    a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.bc1 = 0.f; a.bc2sqrt = 0.f;
+    a.partials = nullptr; a.npartials = 0; a.max_norm = 0.f; a.write_grad = write_grad; a.gscale = 0.f;
+    a.guard = static_cast<const int*>(guard);
+    return adamw_flat_launch<true>(a, st);
 }

@@ -1,11 +1,13 @@
-"""The refine training loop as a public entry (reference engine.py:93-174), built from the device-side pieces of this package: CAM
+"""The refine training loops as public entries (reference engine.py:93-174 and its COCO twin :534-613), built from the device-side pieces of this package: CAM
 pseudo boxes (spe_amd.camboxes), the refine post-processor for the stage-k+1 targets, both criteria, and the step ledger
 (spe_amd.steplog) in place of the reference's per-key loss arithmetic, its `.item()` before the backward and its ~95 `.item()` calls
 after the optimizer step.  Signature, log lines and return value are the reference's.
 
 Difference: a weighted total that is not finite stops the run at the next log line or at the end of the epoch
 (FloatingPointError from the ledger), not before the optimizer step of that iteration; up to print_freq steps of compute are wasted,
-the weights are lost either way (the reference exits without saving).
+the weights are lost either way (the reference exits without saving).  FlatAdamW(..., skip_nonfinite=True) closes the hole from the
+other side: an update whose reduced GRADIENT is not finite is skipped on the device, so the weights in memory survive; a non-finite
+loss with finite gradients is still applied and still stops at the ledger's check.
 
 The evaluation loops `evaluate_det_voc` (reference engine_loc.py:127-201) and `evaluate_refinements` (engine.py:617-724) follow: the
 detection head (spe_amd.infer.detect) between the forward and a detection meter (spe_amd.evalmetrics), DESIGN.md section 8k."""
@@ -67,8 +69,23 @@ def get_refinements_pseudo_label(outputs, samples, targets, args, postprocessors
     return targets_refine
 
 
-def train_one_epoch_refine(model, criterion, data_loader, optimizer, device, epoch, max_norm=0, args=None, postprocessors=None,
-                           criterion_refine=None):
+def apply_curriculum_coco(weight_dict, epoch):
+    """engine.py:573-581, the COCO loop's curriculum: before epoch 1 only the image-label keys keep their weight.  The reference's
+    second block (:578-581) zeroes the keys that contain `header` - there the LOG header string '[<time>] => Epoch: [<n>]', not
+    'ref': it matches no key and changes nothing, so it is restated here as nothing."""
+    if epoch < 1:
+        for k in weight_dict:
+            if "img_label" not in k:
+                weight_dict[k] = 0.0
+    return weight_dict
+
+
+def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, device, epoch, max_norm, args, postprocessors, criterion_refine):
+    """The loop of both public entries; `curriculum(weight_dict, epoch)` is what differs between them.
+
+    Gradient accumulation: with a FlatAdamW whose reducer has accum_steps > 1 every iteration still does zero_grad / backward /
+    finish() and is recorded in the ledger, optimizer.step() runs when finish() completed a cycle, and the micro-batches of a cycle
+    left open at the end of the epoch are dropped (one printed line).  With accum_steps = 1 every finish() completes a cycle."""
     from .optim import FlatAdamW
     model.train()
     criterion.train()
@@ -93,20 +110,42 @@ def train_one_epoch_refine(model, criterion, data_loader, optimizer, device, epo
                 continue
             for k, v in criterion_refine(out, pseudo_label_refine[rf]).items():
                 loss_dict[f"{RF_HEADER}_{rf}_{k}"] = v
-        apply_curriculum(weight_dict, epoch)
+        curriculum(weight_dict, epoch)
 
         losses = ledger.record(loss_dict, weight_dict, lr=optimizer.param_groups[0]["lr"])
         optimizer.zero_grad()
         losses.backward()
         if flat:
             optimizer.reducer.finish()
+            if optimizer.reducer.micro != 0:             # inside an accumulation cycle: the update waits for its last micro-step
+                continue
         elif max_norm > 0:
             torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
         optimizer.step()
 
+    if flat and optimizer.reducer.micro != 0:
+        left = optimizer.reducer.micro
+        optimizer.reducer.restart_cycle()
+        print(f"Dropped the last {left} micro-batch(es) of the epoch: an incomplete accumulation cycle of {optimizer.reducer.accum_steps}")
+    if flat and optimizer.skip_nonfinite and optimizer.skipped_steps() > 0:
+        print(f"Optimizer steps skipped on a non-finite gradient: {optimizer.skipped_steps()} so far, the first at step {optimizer.first_skipped()}")
     stats = ledger.global_avg()                  # synchronised between the ranks; raises if a step's total was not finite
     print("Averaged stats:", ledger)
     return stats
+
+
+def train_one_epoch_refine(model, criterion, data_loader, optimizer, device, epoch, max_norm=0, args=None, postprocessors=None,
+                           criterion_refine=None):
+    """engine.py:93-174 (the VOC loop)."""
+    return _train_one_epoch(apply_curriculum, model, criterion, data_loader, optimizer, device, epoch, max_norm, args, postprocessors,
+                            criterion_refine)
+
+
+def train_one_epoch_refine_coco(model, criterion, data_loader, optimizer, device, epoch, max_norm=0, args=None, postprocessors=None,
+                                criterion_refine=None):
+    """engine.py:534-613 (the loop main_coco.py:356 calls): the same body with the COCO curriculum."""
+    return _train_one_epoch(apply_curriculum_coco, model, criterion, data_loader, optimizer, device, epoch, max_norm, args, postprocessors,
+                            criterion_refine)
 
 
 # ---- evaluation loops (reference engine_loc.py:127-201, engine.py:617-724; DESIGN.md section 8k) -----------------------------------

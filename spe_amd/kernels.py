@@ -1634,6 +1634,22 @@ def adamw_flat(p, g, m, v, seg_end_i64, seg_lr, seg_wd, beta1, beta2, eps, bias_
           float(max_norm), int(bool(write_grad)), float(grad_scale), _st())
 
 
+ADAMW_GUARD_WORDS = 16            # SPE_ADAMW_GUARD_WORDS of include/spe_hip.h
+# the guard block's words: int32 0..3, fp32 4..8 (layout in include/spe_hip.h)
+GUARD_APPLIED, GUARD_SKIPPED, GUARD_FIRST, GUARD_APPLY, GUARD_CLIP, GUARD_BC1, GUARD_BC2SQRT, GUARD_NORM, GUARD_STEP_F = range(9)
+
+
+def adamw_gate(guard_i32, partials, max_norm, grad_scale, beta1, beta2):
+    """The decision of one guarded optimizer step from the squared-norm partials of all buckets, written into the guard block."""
+    _call("spe_adamw_gate", _p(guard_i32), _p(partials), partials.numel(), float(max_norm), float(grad_scale), float(beta1),
+          float(beta2), _st())
+
+
+def adamw_flat_guarded(p, g, m, v, seg_end_i64, seg_lr, seg_wd, beta1, beta2, eps, guard_i32, write_grad):
+    _call("spe_adamw_flat_guarded", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(seg_end_i64), _p(seg_lr), _p(seg_wd), seg_end_i64.numel(),
+          float(beta1), float(beta2), float(eps), _p(guard_i32), int(bool(write_grad)), _st())
+
+
 def accum_flat(dst, a, b=None):
     """dst = a + b on flat fp32 buffers of equal size (dst may be a or b); b None: dst = a, bit for bit."""
     _chk(dst, a, b)

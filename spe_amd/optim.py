@@ -9,6 +9,10 @@ reduced from per-block partial sums inside the update kernel (no host round trip
 rate / weight decay come from a small segment table.  FlatAdamW is a torch.optim.Optimizer: `param_groups`,
 LR schedulers (StepLR in the reference) and state_dict()/load_state_dict() keep working; the per-parameter state
 entries are views into the flat moment buffers.
+
+FlatAdamW(..., skip_nonfinite=True) is the guarded step: one more one-workgroup launch decides on the device, from the norm partials
+that are there anyway, whether the reduced gradient is finite, and the update launches leave parameters, moments and gradients
+untouched when it is not (see the class docstring).
 """
 import torch
 
@@ -19,8 +23,25 @@ _NORM_BLOCKS = 256
 
 
 class FlatAdamW(torch.optim.Optimizer):
+    """skip_nonfinite=False: two launches per bucket (one without clipping), bias corrections from the host's step count.
+
+    skip_nonfinite=True: every step() runs the squared-norm pass of every bucket (also with max_grad_norm unset: no clip then), ONE gate
+    launch (spe_adamw_gate) and one guarded update per bucket (spe_adamw_flat_guarded).  The gate sums the partials and applies the
+    step only if that sum is finite: a NaN or an infinity anywhere in the gradient buckets skips it, and so does a squared norm that
+    overflows fp32 (one element beyond ~1.8e19).  A skipped step writes nothing - parameters, both moments and the gradient buckets
+    keep their bits - and does not advance the bias corrections: they follow the count of APPLIED steps, kept on the device, so the
+    run continues as if the bad iteration had not happened.  step() reads nothing back; applied_steps(), skipped_steps() and
+    first_skipped() are the host reads (each one small device-to-host copy: they synchronise).  `_step` counts attempts; the
+    per-parameter `step` entries are one 0-dim device tensor inside the guard block that holds the applied count.
+    * Gradient accumulation needs nothing special: a non-finite micro-step makes the accumulated sum non-finite, and the whole
+      cycle is skipped.
+    * Several ranks: the decision is a function of the all-reduced buckets only, which are identical on every rank, so every rank
+      takes the same decision without a further collective.
+    * Only the gradient decides.  A non-finite LOSS whose gradients are all finite is still applied; the step ledger
+      (spe_amd.steplog) stops such a run at its next check, as before."""
+
     def __init__(self, params, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
-                 write_clipped_grads=True):
+                 write_clipped_grads=True, skip_nonfinite=False):
         if not getattr(reducer, "flatten_params", False):
             raise ValueError("FlatAdamW needs GradAllReducer(..., flatten_params=True)")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -42,9 +63,17 @@ class FlatAdamW(torch.optim.Optimizer):
             for p in grp["params"]:
                 gid[p] = gi
         self._step = 0
+        self.skip_nonfinite = bool(skip_nonfinite)
+        dev = reducer.buckets[0]["flat"].device
         # ONE 0-dim step tensor shared by every parameter's state entry (torch.optim.AdamW semantics: optimizer.state[p]["step"] is always
-        # current) and bumped by a single host op per step() - not 717 tensor increments
-        self._step_t = torch.zeros((), dtype=torch.float32)
+        # current) and bumped by a single host op per step() - not 717 tensor increments.  Guarded: the applied count lives on the
+        # device, so the shared tensor is the guard block's float copy of it, written by the gate launch.
+        self._guard = None
+        if self.skip_nonfinite:
+            self._guard = torch.zeros((K.ADAMW_GUARD_WORDS,), device=dev, dtype=torch.int32)
+            self._step_t = self._guard.view(torch.float32)[K.GUARD_STEP_F]
+        else:
+            self._step_t = torch.zeros((), dtype=torch.float32)
         self._buckets = []
         for b in reducer.buckets:
             n = b["flat"].numel()
@@ -68,7 +97,6 @@ class FlatAdamW(torch.optim.Optimizer):
                 raise ValueError("FlatAdamW: more than 64 parameter-group runs in one bucket")
             self._buckets.append({"b": b, "m": m, "v": v, "groups": groups,
                                   "seg_end": host_to_device(ends, torch.int64, m.device), "tab": None, "tab_key": None})
-        dev = reducer.buckets[0]["flat"].device
         self._partials = torch.zeros((_NORM_BLOCKS * len(self._buckets),), device=dev, dtype=torch.float32)
 
     @torch.no_grad()
@@ -81,14 +109,18 @@ class FlatAdamW(torch.optim.Optimizer):
             raise RuntimeError(f"FlatAdamW.step() inside an accumulation cycle: micro-step {self.reducer.micro} of accum_steps = "
                                f"{self.reducer.accum_steps} comes next - run the remaining backward passes (or reducer.restart_cycle())")
         self._step += 1
-        self._step_t += 1
+        guarded = self.skip_nonfinite
+        if not guarded:
+            self._step_t += 1
         b1, b2 = self.param_groups[0]["betas"]
         eps = self.param_groups[0]["eps"]
         bc1, bc2 = 1.0 - b1 ** self._step, 1.0 - b2 ** self._step
         clip = float(self.max_grad_norm) if self.max_grad_norm else 0.0
-        if clip > 0:
+        if clip > 0 or guarded:
             for i, e in enumerate(self._buckets):
                 K.sqnorm_partials(e["b"]["flat"], self._partials[i * _NORM_BLOCKS:(i + 1) * _NORM_BLOCKS])
+        if guarded:
+            K.adamw_gate(self._guard, self._partials, clip, self.reducer.grad_scale(), b1, b2)
         for e in self._buckets:
             key = tuple((self.param_groups[g]["lr"], self.param_groups[g]["weight_decay"]) for g in e["groups"])
             if key != e["tab_key"]:            # LR scheduler moved: refresh the (tiny) per-segment table
@@ -96,21 +128,44 @@ class FlatAdamW(torch.optim.Optimizer):
                 e["tab"] = (host_to_device([k[0] for k in key], torch.float32, dev),
                             host_to_device([k[1] for k in key], torch.float32, dev))
                 e["tab_key"] = key
-            K.adamw_flat(e["b"]["flat_p"], e["b"]["flat"], e["m"], e["v"], e["seg_end"], e["tab"][0], e["tab"][1],
-                         b1, b2, eps, bc1, bc2, self._partials, clip, self.write_clipped_grads,
-                         grad_scale=self.reducer.grad_scale())
+            if guarded:
+                K.adamw_flat_guarded(e["b"]["flat_p"], e["b"]["flat"], e["m"], e["v"], e["seg_end"], e["tab"][0], e["tab"][1],
+                                     b1, b2, eps, self._guard, self.write_clipped_grads)
+            else:
+                K.adamw_flat(e["b"]["flat_p"], e["b"]["flat"], e["m"], e["v"], e["seg_end"], e["tab"][0], e["tab"][1],
+                             b1, b2, eps, bc1, bc2, self._partials, clip, self.write_clipped_grads,
+                             grad_scale=self.reducer.grad_scale())
         K.weights_changed()            # the update bypassed autograd's version counters: drop cached bf16 weight copies
         return loss
+
+    def _guard_counts(self):
+        if self._guard is None:
+            raise RuntimeError("FlatAdamW: applied_steps() / skipped_steps() / first_skipped() need skip_nonfinite=True")
+        return self._guard[:3].tolist()
+
+    def applied_steps(self):
+        """Steps the guard applied so far.  A device-to-host copy: synchronises."""
+        return self._guard_counts()[K.GUARD_APPLIED]
+
+    def skipped_steps(self):
+        """Steps the guard skipped so far (since construction or the last load_state_dict()).  Synchronises."""
+        return self._guard_counts()[K.GUARD_SKIPPED]
+
+    def first_skipped(self):
+        """1-based index, among the step() calls, of the first skipped step; 0 if none was skipped.  Synchronises."""
+        return self._guard_counts()[K.GUARD_FIRST]
 
     def state_dict(self):
         """torch's format.  Inside this optimizer every parameter's `step` entry is the one shared, always current tensor; the EXPORTED
         dict gives each parameter its own copy: pickle / torch.save keep aliasing, and torch.optim.AdamW (the reference's optimizer,
         main.py:189-191 and its resume path :224-232) bumps every entry of the list it is handed - one shared tensor would advance by
-        the parameter count per step after such a resume."""
+        the parameter count per step after such a resume.  The inner dicts are copies: torch hands out the live per-parameter dicts
+        of optimizer.state, and a clone written into those would cut optimizer.state[p]["step"] off the shared tensor.
+        Guarded: `step` is the APPLIED count, read from the device (synchronises)."""
         sd = super().state_dict()
-        for st in sd["state"].values():
-            if "step" in st:
-                st["step"] = self._step_t.clone()
+        step = float(self.applied_steps()) if self.skip_nonfinite else float(self._step)
+        sd["state"] = {k: ({**st, "step": torch.tensor(step, dtype=torch.float32)} if "step" in st else dict(st))
+                       for k, st in sd["state"].items()}
         return sd
 
     def zero_grad(self, set_to_none=True):
@@ -120,7 +175,9 @@ class FlatAdamW(torch.optim.Optimizer):
         self.reducer.reset()
 
     def load_state_dict(self, state_dict):
-        """Standard torch format; the moments are copied INTO the flat buffers (the views must stay views)."""
+        """Standard torch format; the moments are copied INTO the flat buffers (the views must stay views).  Guarded: the loaded count
+        becomes the applied count of the guard block (skipped and first-skipped start again at 0), so a guarded run resumed from its
+        own checkpoint continues bit for bit."""
         views = {p: (self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for g in self.param_groups for p in g["params"]}
         super().load_state_dict(state_dict)
         steps = []
@@ -135,6 +192,8 @@ class FlatAdamW(torch.optim.Optimizer):
                     steps.append(int(st["step"]))
         if steps:
             self._step = max(steps)
+        if self.skip_nonfinite:
+            self._guard.copy_(host_to_device([self._step] + [0] * (K.ADAMW_GUARD_WORDS - 1), torch.int32, self._guard.device))
         self._step_t.fill_(float(self._step))
         for g in self.param_groups:                 # re-share the step tensor (load_state_dict gave every parameter its own copy)
             for p in g["params"]:
