@@ -42,7 +42,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_resample_plan / _tables / _h / _v (the input transforms: Pillow-exact bilinear resize, crop, flip, normalise, pad),
  * spe_ledger_state_bytes / _record / _total_bwd / _summary (the step ledger: weighted total, loss meters and non-finite guard on the device)
  * spe_gemm_f32_plan (the kernel selection and launch choices of spe_gemm_f32 / spe_gemm_ex, host only)
- * - 100 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
+ * spe_jpeg_probe / _entropy / _reconstruct (baseline JPEG decoding: host entropy pass, device IDCT to RGB)
+ * - 106 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -701,6 +702,47 @@ int spe_resample_tables(const long* desc_host, const long* desc_dev, int n, int*
 int spe_resample_h(const long* desc_host, const long* desc_dev, int n, const int* tables, unsigned char* tmp, spe_stream_t stream);
 int spe_resample_v(const long* desc_host, const long* desc_dev, int n, const int* tables, const unsigned char* tmp, const float* lut,
                    float* out, unsigned char* mask, int Hmax, int Wmax, spe_stream_t stream);
+
+/* ---- baseline JPEG decoding: the step in front of the transforms (the reference's datasets/voc.py and coco.py open every file
+ * with PIL in __getitem__; csrc/jpeg_entropy.h + csrc/jpeg_decode.hip).  The result equals libjpeg-turbo's default decode - islow
+ * IDCT, fancy upsampling, 16-bit fixed-point colour tables: what Pillow returns - bit for bit.
+ * Host (plain C++, no HIP call, no global state: thread safe; data / info / coef / reason are HOST pointers):
+ * spe_jpeg_probe: parses the markers up to the scan.  info [SPE_JPEG_INFO_INTS] ints: 0 width, 1 height, 2 components (1 or 3),
+ *   3 / 4 luma sampling h / v, 5 restart interval, 6 / 7 MCUs across / down, 8.. / 11.. h / v per component, 14.. / 17.. blocks
+ *   across / down per component (the grid padded to whole MCUs), 20.. blocks per component, 23 blocks in all, 24 the reason of a
+ *   refusal, 25 offset of the entropy-coded data, 32.. the 8-bit quantisation table of every component, 64 values in natural order.
+ * spe_jpeg_entropy: Huffman-decodes the one scan into coef: quantised int16 [blocks][64] in natural order, the components one
+ *   after the other, each in raster order over its padded block grid; all blocks * 64 elements are written (zeros past an end of
+ *   block).  coef_elems: elements the caller owns.  reason: NULL or one int.
+ * Accepted: SOF0 with 8-bit samples and tables, one component or three with luma 1x1 / 2x1 / 2x2 over 1x1 chroma in one
+ *   interleaved scan; DRI / RSTn; APPn and COM are skipped; EOI may be missing once every MCU is decoded.
+ * Status: SPE_JPEG_UNSUPPORTED progressive, extended / lossless / arithmetic, 12-bit samples, 16-bit tables, two or four
+ *   components, other sampling factors, several scans, Adobe APP14 with a transform other than 1, component ids R G B;
+ *   SPE_JPEG_CORRUPT truncated data, a bad marker or segment length, a missing table, an undefined Huffman code, a run past
+ *   coefficient 63, a wrong restart marker or unread bytes in front of one, a frame of more blocks than the data could hold at two
+ *   bits a block (probe already: nobody allocates for a made-up size); -2 info NULL or coef too small.  No input makes either read or write outside
+ *   [data, data + n) and the caller's buffers.
+ * Device: spe_jpeg_reconstruct, two launches for n images, each through JD_DESC = 16 longs of a descriptor table that exists twice
+ *   with equal content (desc_host validated, sizing the grids; desc_dev read by the kernels).  Fields: 0 W, 1 H, 2 components,
+ *   3 / 4 luma sampling h / v, 5 / 6 MCUs across / down, 7 offset (int16 elements, a multiple of 8) of the image's record in coef,
+ *   8 offset (bytes, a multiple of 16) of its planes in `planes`, 9 dst (device pointer, uint8 [H][W][3], any byte address).
+ *   A record: 192 int16 (the three tables of spe_jpeg_probe) + blocks * 64 coefficients of spe_jpeg_entropy; planes: 64 bytes a block.
+ *   Pass A: x = coef * q, jidctint.c's 8-point pass down the columns (descale 11) and along the rows (descale 18), the range limit
+ *   t = (v + 128) & 1023, t < 256 ? t : t < 640 ? 255 : 0 -> uint8 planes.  Pass B: of a chroma plane ceil(W h / hmax) x
+ *   ceil(H v / vmax) samples are real and neighbours clamp to them; 2x1: (3c + l + 1) >> 2, (3c + r + 2) >> 2; 2x2: s = 3c + the row
+ *   above (even rows) / below (odd rows), then (3s + l + 8) >> 4, (3s + r + 7) >> 4; two or fewer real samples a row:
+ *   replication instead; R = y + ((91881 cr + 32768) >> 16), G = y + ((-22554 cb - 46802 cr + 32768) >> 16), B = y + ((116130 cb + 32768)
+ *   >> 16), clamped; one component: R = G = B = y.  Every byte of dst is written and nothing behind it: 4-byte stores where the
+ *   address is aligned, byte stores at a row's head and tail.
+ *   Status -2, nothing launched: n outside 1 .. 65535, a side outside 1 .. 32768, sampling or MCU counts that do not fit W and H,
+ *   records or planes misaligned, overlapping, out of order or outside coef_elems / planes_bytes, dst 0, coef / planes not 16-B aligned. */
+#define SPE_JPEG_UNSUPPORTED (-7)
+#define SPE_JPEG_CORRUPT (-8)
+#define SPE_JPEG_INFO_INTS 224
+int spe_jpeg_probe(const unsigned char* data, long n, int* info);
+int spe_jpeg_entropy(const unsigned char* data, long n, short* coef, long coef_elems, int* reason);
+int spe_jpeg_reconstruct(const long* desc_host, const long* desc_dev, int n, const short* coef, long coef_elems,
+                         unsigned char* planes, long planes_bytes, spe_stream_t stream);
 
 /* ---- step ledger: the loss bookkeeping of a training step (reference engine.py:134-169, util/misc.py:34-93, 139-253;
  * csrc/step_ledger.hip, compiled without FMA contraction).  K loss values per step (1 <= K <= 256), E host scalars such as lr

@@ -2002,3 +2002,52 @@ def resample_batch(jobs, lut=None, out=None, mask=None):
         return out, mask
     _call("spe_resample_v", desc.data_ptr(), _p(ddev), n, _p(tables), _p(tmp), None, None, None, 0, 0, st)
     return dsts
+
+
+# ---- baseline JPEG decoding: host entropy pass, IDCT to RGB on the device (csrc/jpeg_entropy.h, csrc/jpeg_decode.hip) --------------
+JPEG_UNSUPPORTED, JPEG_CORRUPT = -7, -8      # statuses of spe_jpeg_probe / spe_jpeg_entropy (include/spe_hip.h)
+JPEG_INFO_INTS = 224
+JPEG_DESC = 16             # longs per image descriptor
+JPEG_QT = 192              # int16 in front of an image's coefficients: its three quantisation tables
+JPEG_MAX_SIDE = 32768
+
+
+def jpeg_probe(data):
+    """Host only.  data: bytes -> (status, info): int32 [JPEG_INFO_INTS] as include/spe_hip.h lays it out."""
+    info = torch.zeros((JPEG_INFO_INTS,), dtype=torch.int32)
+    return lib.load().spe_jpeg_probe(data, len(data), info.data_ptr()), info
+
+
+def jpeg_entropy(data, coef):
+    """Host only; ctypes releases the GIL for the call.  coef: a contiguous int16 HOST tensor, every block's 64 coefficients are
+    written.  -> (status, reason)."""
+    if coef.is_cuda or coef.dtype != torch.int16 or not coef.is_contiguous():
+        raise TypeError("jpeg_entropy: expected a contiguous int16 host tensor")
+    reason = ctypes.c_int(0)
+    rc = lib.load().spe_jpeg_entropy(data, len(data), coef.data_ptr(), coef.numel(), ctypes.addressof(reason))
+    return rc, reason.value
+
+
+def jpeg_reconstruct(frames, coef, dsts=None):
+    """The two launches for a batch.  frames: [(W, H, ncomp, hs, vs, mcux, mcuy, offset), ...] - offset: where in coef (int16, on the
+    device) the image's record begins, JPEG_QT table entries and then blocks * 64 coefficients.  dsts: uint8 tensors of H * W * 3
+    bytes each, at any byte address (default: fresh [H,W,3] tensors).  -> dsts."""
+    n = len(frames)
+    if n == 0:
+        raise ValueError("jpeg_reconstruct: no images")
+    _check_typed("jpeg_reconstruct", [(coef, torch.int16)] + [(t, torch.uint8) for t in dsts or []])
+    dev = coef.device
+    if dsts is None:
+        dsts = [torch.empty((max(int(f[1]), 0), max(int(f[0]), 0), 3), device=dev, dtype=torch.uint8) for f in frames]
+    desc = torch.zeros((n, JPEG_DESC), dtype=torch.int64)
+    planes_bytes = 0
+    for i, (f, dst) in enumerate(zip(frames, dsts)):
+        W, H, nc, hs, vs, mcux, mcuy, off = (int(v) for v in f)
+        if dst.device != dev or dst.numel() != H * W * 3:
+            raise ValueError("jpeg_reconstruct: dst must hold H * W * 3 bytes on the coefficients' device")
+        desc[i, :10] = torch.tensor([W, H, nc, hs, vs, mcux, mcuy, off, planes_bytes, dst.data_ptr()], dtype=torch.int64)
+        planes_bytes += max(mcux * mcuy * (1 if nc == 1 else hs * vs + 2), 0) * 64
+    planes = torch.empty((max(planes_bytes, 16),), device=dev, dtype=torch.uint8)
+    ddev = desc.to(dev, non_blocking=True)
+    _call("spe_jpeg_reconstruct", desc.data_ptr(), _p(ddev), n, _p(coef), coef.numel(), _p(planes), planes_bytes, _st())
+    return dsts

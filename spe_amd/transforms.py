@@ -7,7 +7,10 @@ flip folded into the source index map, ToTensor + Normalize as a 3 x 256 table a
 
 Random numbers are drawn exactly where the reference draws them, in the same order, from the same generators (Python's `random`;
 `torch.randint` for the crop origin, with torchvision's RandomCrop.get_params semantics since 0.8).  The target side runs eagerly
-on the host with the reference's fp32 torch operations.  Segmentation masks, RandomPad and RandomErasing are not built."""
+on the host with the reference's fp32 torch operations.  Segmentation masks, RandomPad and RandomErasing are not built.
+
+decode_jpeg turns file bytes into DeviceImages (spe_amd.jpeg: Huffman decoding on the host, everything after it on the device), so a
+loader can hand the files through as they are."""
 import random
 
 import torch
@@ -59,6 +62,13 @@ class DeviceImage:
     def resize(self, oh, ow):
         st = self.stages + (self.box + (self.flip, int(oh), int(ow)),)
         return self._new(st, (0, 0, int(ow), int(oh)), False)
+
+
+def decode_jpeg(datas, device="cuda", **kw):
+    """[file bytes, ...] -> [DeviceImage, ...], equal to DeviceImage(np.asarray(Image.open(f).convert("RGB"))) bit for bit.  Keyword
+    arguments go to spe_amd.jpeg.decode_batch (threads, fallback)."""
+    from . import jpeg
+    return [DeviceImage(t, device=device) for t in jpeg.decode_batch(datas, device=device, **kw)]
 
 
 class PendingTensor:
