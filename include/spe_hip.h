@@ -43,7 +43,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_ledger_state_bytes / _record / _total_bwd / _summary (the step ledger: weighted total, loss meters and non-finite guard on the device)
  * spe_gemm_f32_plan (the kernel selection and launch choices of spe_gemm_f32 / spe_gemm_ex, host only)
  * spe_jpeg_probe / _entropy / _reconstruct (baseline JPEG decoding: host entropy pass, device IDCT to RGB)
- * - 106 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
+ * spe_adamw_flat_ema / spe_swap_flat (the weight EMA kept inside the optimizer's update launch, and its exchange with the parameters)
+ * - 108 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -823,6 +824,24 @@ int spe_adamw_flat_guarded(float* p, float* g, float* m, float* v, long n, const
  * Every pointer 16-B aligned (-2 otherwise, nothing written); n <= 0: nothing launched.  No atomics, no cross-lane sums:
  * bitwise deterministic. */
 int spe_accum_flat(float* dst, const float* a, const float* b, long n, spe_stream_t stream);
+
+/* ---- weight EMA inside the update launch (no reference site: the reference's evaluate / evaluate_refinements, engine.py:448 and
+ * :617, read the last iterate; the DETR family's usual remedy for a noisy last iterate, kept here as one more fp32 stream of the launch that exists anyway).
+ * spe_adamw_flat_ema: spe_adamw_flat (guard == NULL) or spe_adamw_flat_guarded (guard != NULL: the block of spe_adamw_gate; bias_c1,
+ * bias_c2, partials, npartials, max_norm, grad_scale and t are then ignored) with one more flat buffer e of the same layout:
+ *     e'[i] = e[i] + w * (p'[i] - e[i])        three fp32 operations, each rounded (no FMA), p' the parameter just computed
+ *     w = (float)(1 - d),  d = warmup ? min(decay, (1 + t) / (10 + t)) : decay    in fp64, rounded once
+ * t: the 1-based count of applied steps including this one - the argument (unguarded) or word [8] of the guard block (guarded).  p,
+ * g, m and v get the bits the entry without the EMA leaves.  Padding elements are averaged like the rest.  A guarded launch that
+ * reads apply == 0 writes nothing: e keeps its bits and the warm-up does not advance.  Status as the two entries above; -2 also for
+ * e NULL or not 16-B aligned and for decay outside [0, 1) (NaN included).  One kernel body and one launch helper serve all three entries.
+ * spe_swap_flat: exchanges the bits of a[0 .. n) and b[0 .. n) (loads and stores only: NaN payloads and -0.0 survive); the grid of
+ * spe_accum_flat.  -2: a pointer NULL or not 16-B aligned, a == b; n <= 0: nothing launched. */
+int spe_adamw_flat_ema(float* p, float* g, float* m, float* v, float* e, long n, const long* seg_end, const float* seg_lr,
+                       const float* seg_wd, int nseg, float beta1, float beta2, float eps, float bias_c1, float bias_c2,
+                       const float* partials, int npartials, float max_norm, int write_grad, float grad_scale,
+                       const void* guard, double decay, int warmup, long t, spe_stream_t stream);
+int spe_swap_flat(float* a, float* b, long n, spe_stream_t stream);
 
 /* ---- diagnostic (never launched by the product): keep nwg workgroups resident for `micros` microseconds, streaming copies
  * through buf (buf_floats floats, 16-B aligned; NULL: idle spinning) - the one-GPU proxy for the CU / HBM share of an RCCL ring

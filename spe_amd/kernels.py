@@ -1650,6 +1650,23 @@ def adamw_flat_guarded(p, g, m, v, seg_end_i64, seg_lr, seg_wd, beta1, beta2, ep
           float(beta1), float(beta2), float(eps), _p(guard_i32), int(bool(write_grad)), _st())
 
 
+def adamw_flat_ema(p, g, m, v, e, seg_end_i64, seg_lr, seg_wd, beta1, beta2, eps, write_grad, decay, warmup, guard_i32=None, bias_c1=1.0,
+                   bias_c2=1.0, partials=None, max_norm=0.0, grad_scale=1.0, t=0):
+    """adamw_flat (guard_i32 None: bias corrections, partials, clip, scale and the applied count t from the caller) or
+    adamw_flat_guarded (those from the guard block) with the weight EMA e kept in the same launch (spe_adamw_flat_ema)."""
+    _call("spe_adamw_flat_ema", _p(p), _p(g), _p(m), _p(v), _p(e), p.numel(), _p(seg_end_i64), _p(seg_lr), _p(seg_wd), seg_end_i64.numel(),
+          float(beta1), float(beta2), float(eps), float(bias_c1), float(bias_c2), _p(partials), 0 if partials is None else partials.numel(),
+          float(max_norm), int(bool(write_grad)), float(grad_scale), _p(guard_i32), float(decay), int(bool(warmup)), int(t), _st())
+
+
+def swap_flat(a, b):
+    """Exchange the bits of two flat fp32 buffers of equal size (spe_swap_flat)."""
+    _chk(a, b)
+    if a.numel() != b.numel() or not (a.is_contiguous() and b.is_contiguous()):
+        raise ValueError("swap_flat: two contiguous buffers with the same number of elements")
+    _call("spe_swap_flat", _p(a), _p(b), a.numel(), _st())
+
+
 def accum_flat(dst, a, b=None):
     """dst = a + b on flat fp32 buffers of equal size (dst may be a or b); b None: dst = a, bit for bit."""
     _chk(dst, a, b)

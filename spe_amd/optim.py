@@ -13,7 +13,12 @@ entries are views into the flat moment buffers.
 FlatAdamW(..., skip_nonfinite=True) is the guarded step: one more one-workgroup launch decides on the device, from the norm partials
 that are there anyway, whether the reduced gradient is finite, and the update launches leave parameters, moments and gradients
 untouched when it is not (see the class docstring).
+
+FlatAdamW(..., ema_decay=d) keeps an exponential moving average of the weights as one more flat fp32 buffer per bucket, updated by the
+update launch itself; `with optimizer.ema_weights():` swaps it into the parameters for an evaluation (see the class docstring).
 """
+import contextlib
+
 import torch
 
 from . import kernels as K
@@ -38,10 +43,26 @@ class FlatAdamW(torch.optim.Optimizer):
     * Several ranks: the decision is a function of the all-reduced buckets only, which are identical on every rank, so every rank
       takes the same decision without a further collective.
     * Only the gradient decides.  A non-finite LOSS whose gradients are all finite is still applied; the step ledger
-      (spe_amd.steplog) stops such a run at its next check, as before."""
+      (spe_amd.steplog) stops such a run at its next check, as before.
+
+    ema_decay=d (0 <= d < 1; None: off, nothing allocated, the entries without the EMA are called): one more flat buffer per bucket,
+    a bit copy of the parameters at construction, updated by every APPLIED step() inside the update launch (spe_adamw_flat_ema: the
+    same number of launches, nothing read back) and by nothing else:
+        e' = e + w * (p' - e)  in fp32,  w = float(1 - min(d, (1 + t) / (10 + t)))  (ema_warmup=False: w = float(1 - d))
+    with p' the parameter the step has just computed and t the 1-based count of applied steps - a skipped step leaves the EMA and the
+    warm-up where they were, and with gradient accumulation the EMA moves once per completed cycle.  Parameters are identical on
+    every rank, so the EMA is too: no collective.
+    * ema_of(p): a view into the EMA buffer shaped like p.  ema_state_dict(model) / load_ema_state_dict(model, sd): the EMA in the
+      layout of model.state_dict() (a checkpoint's "model_ema").  state_dict() / load_state_dict() neither export nor touch it.
+    * `with optimizer.ema_weights(): evaluate(...)` exchanges parameters and EMA on entry and again on exit (one spe_swap_flat per
+      bucket, cached 16-bit operand copies invalidated both times).  Inside the block step(), ema_reset(), ema_state_dict(),
+      load_ema_state_dict() and a second ema_weights() raise RuntimeError.
+    * ema_reset(): see there - needed when model weights are loaded after the optimizer was built."""
 
     def __init__(self, params, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
-                 write_clipped_grads=True, skip_nonfinite=False):
+                 write_clipped_grads=True, skip_nonfinite=False, ema_decay=None, ema_warmup=True):
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:          # NaN fails the comparison too
+            raise ValueError(f"FlatAdamW: ema_decay must be None or in [0, 1), got {ema_decay}")
         if not getattr(reducer, "flatten_params", False):
             raise ValueError("FlatAdamW needs GradAllReducer(..., flatten_params=True)")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -74,10 +95,15 @@ class FlatAdamW(torch.optim.Optimizer):
             self._step_t = self._guard.view(torch.float32)[K.GUARD_STEP_F]
         else:
             self._step_t = torch.zeros((), dtype=torch.float32)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self._ema_swapped = False
+        self._ema_views = {}
         self._buckets = []
         for b in reducer.buckets:
             n = b["flat"].numel()
             m, v = torch.zeros_like(b["flat"]), torch.zeros_like(b["flat"])
+            ema = torch.zeros_like(b["flat_p"]) if self.ema_decay is not None else None
             # runs of consecutive parameters of one group -> (segment end, group); padding follows its parameter
             ends, groups = [], []
             offs = b["offsets"]
@@ -93,11 +119,15 @@ class FlatAdamW(torch.optim.Optimizer):
                 st["step"] = self._step_t
                 st["exp_avg"] = m[off:off + p.numel()].view_as(p)
                 st["exp_avg_sq"] = v[off:off + p.numel()].view_as(p)
+                if ema is not None:
+                    self._ema_views[p] = ema[off:off + p.numel()].view_as(p)
             if len(ends) > 64:
                 raise ValueError("FlatAdamW: more than 64 parameter-group runs in one bucket")
-            self._buckets.append({"b": b, "m": m, "v": v, "groups": groups,
+            self._buckets.append({"b": b, "m": m, "v": v, "ema": ema, "groups": groups,
                                   "seg_end": host_to_device(ends, torch.int64, m.device), "tab": None, "tab_key": None})
         self._partials = torch.zeros((_NORM_BLOCKS * len(self._buckets),), device=dev, dtype=torch.float32)
+        if self.ema_decay is not None:
+            self.ema_reset()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -108,6 +138,7 @@ class FlatAdamW(torch.optim.Optimizer):
         if getattr(self.reducer, "micro", 0) != 0:
             raise RuntimeError(f"FlatAdamW.step() inside an accumulation cycle: micro-step {self.reducer.micro} of accum_steps = "
                                f"{self.reducer.accum_steps} comes next - run the remaining backward passes (or reducer.restart_cycle())")
+        self._ema_check("step()", need_ema=False)
         self._step += 1
         guarded = self.skip_nonfinite
         if not guarded:
@@ -128,7 +159,12 @@ class FlatAdamW(torch.optim.Optimizer):
                 e["tab"] = (host_to_device([k[0] for k in key], torch.float32, dev),
                             host_to_device([k[1] for k in key], torch.float32, dev))
                 e["tab_key"] = key
-            if guarded:
+            if e["ema"] is not None:           # the same launch with the EMA stream; unguarded: _step is the applied count
+                K.adamw_flat_ema(e["b"]["flat_p"], e["b"]["flat"], e["m"], e["v"], e["ema"], e["seg_end"], e["tab"][0], e["tab"][1],
+                                 b1, b2, eps, self.write_clipped_grads, self.ema_decay, self.ema_warmup,
+                                 guard_i32=self._guard if guarded else None, bias_c1=bc1, bias_c2=bc2, partials=self._partials,
+                                 max_norm=clip, grad_scale=self.reducer.grad_scale(), t=self._step)
+            elif guarded:
                 K.adamw_flat_guarded(e["b"]["flat_p"], e["b"]["flat"], e["m"], e["v"], e["seg_end"], e["tab"][0], e["tab"][1],
                                      b1, b2, eps, self._guard, self.write_clipped_grads)
             else:
@@ -137,6 +173,68 @@ class FlatAdamW(torch.optim.Optimizer):
                              grad_scale=self.reducer.grad_scale())
         K.weights_changed()            # the update bypassed autograd's version counters: drop cached bf16 weight copies
         return loss
+
+    # ---- weight EMA ------------------------------------------------------------------------------------------------------------
+    def _ema_check(self, what, need_ema=True):
+        if need_ema and self.ema_decay is None:
+            raise RuntimeError(f"FlatAdamW.{what} needs ema_decay (the optimizer was built without a weight EMA)")
+        if self._ema_swapped:
+            raise RuntimeError(f"FlatAdamW.{what} inside `with optimizer.ema_weights()`: the parameters hold the EMA there")
+
+    def ema_of(self, p):
+        """The EMA of parameter p: a view into the flat EMA buffer, shaped like p (it shows the buffer as it is now; inside
+        ema_weights() that is the training weights)."""
+        if self.ema_decay is None:
+            raise RuntimeError("FlatAdamW.ema_of() needs ema_decay (the optimizer was built without a weight EMA)")
+        return self._ema_views[p]
+
+    @torch.no_grad()
+    def ema_reset(self):
+        """EMA := the current parameters, bit for bit.  The constructor does this; call it again after loading model weights into an
+        optimizer that already exists - the reference's resume order builds the optimizer first and calls model.load_state_dict()
+        afterwards, and the EMA would otherwise still average the initial weights (a checkpoint with a "model_ema" entry is
+        restored with load_ema_state_dict() instead).  The warm-up is not reset: it follows the count of applied steps."""
+        self._ema_check("ema_reset()")
+        for e in self._buckets:
+            K.accum_flat(e["ema"], e["b"]["flat_p"])
+
+    @torch.no_grad()
+    def ema_state_dict(self, model):
+        """A dict with the keys and shapes of model.state_dict(): clones of the EMA for the parameters this optimizer owns, clones of
+        the current values for everything else.  model.load_state_dict() of a plain model consumes it."""
+        self._ema_check("ema_state_dict()")
+        return {k: (self._ema_views[v] if v in self._ema_views else v).detach().clone()
+                for k, v in model.state_dict(keep_vars=True).items()}
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, model, sd):
+        """The inverse of ema_state_dict(): the entries of the parameters this optimizer owns are copied INTO the flat EMA buffer (the
+        views stay views); the other entries belong to the model and are ignored here."""
+        self._ema_check("load_ema_state_dict()")
+        for k, v in model.state_dict(keep_vars=True).items():
+            if v in self._ema_views:
+                if tuple(sd[k].shape) != tuple(v.shape):
+                    raise ValueError(f"load_ema_state_dict: {k} has shape {tuple(sd[k].shape)}, the parameter {tuple(v.shape)}")
+                self._ema_views[v].copy_(sd[k])
+
+    def _ema_swap(self):
+        for e in self._buckets:
+            K.swap_flat(e["b"]["flat_p"], e["ema"])
+        K.weights_changed()            # the parameters changed behind autograd's version counters: drop cached 16-bit copies
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model's parameters ARE the EMA, bit for bit (and the EMA buffer holds the training weights); on exit -
+        also through an exception - both buffers have their earlier bits again.  For evaluation:
+            with optimizer.ema_weights(): evaluate_det_voc(model, ...)"""
+        self._ema_check("ema_weights()")
+        self._ema_swap()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swap()
+            self._ema_swapped = False
 
     def _guard_counts(self):
         if self._guard is None:
