@@ -150,7 +150,13 @@ int spe_layernorm_bwd_ls(const float* dy, const float* x, const float* gamma, co
  *   y = x W^T: (x16, W16) ; dx = dy W: (dy16, W16T) ; dW = dy^T x: (dy16T, x16T), contraction zero padded.
  * spe_cvt_bf16: out[R][ldo] = bf16(x) (round to nearest even, the rounding spe_gemm_f32 applies while staging)
  * and/or outT[C][ldt] = transpose, columns R..ldt-1 zero filled; colsum[c] += sum_r x[r][c] (fp32; the bias gradient
- * of the Linear, from the same read).  Any of the three outputs may be NULL.  aux != NULL: x is first multiplied by the
+ * of the Linear, from the same read).  Any of the three outputs may be NULL.  Alignment: x and aux need only their 4 bytes (rows are
+ * read as 16-byte vectors when ldx % 4 == 0 and x is 16-byte aligned, element by element otherwise); out / out_lo must be 8-byte aligned
+ * when ldo % 4 == 0 and outT when ldt % 4 == 0 (quads are then stored as 8-byte vectors; any other ldo / ldt: 2-byte stores, 2-byte
+ * alignment) - a column block of a wider bf16 matrix therefore starts at a column that is a multiple of 4.  ldt may exceed R by any
+ * amount: all of columns R..ldt-1 are zero filled.  Measured on the MI355X (tests/test_cvt16_gpu.py, profiles/cvt16_edges.txt): fp32
+ * subnormal inputs are converted like any other value - the bf16 copy keeps them as bf16 subnormals, rounded to nearest even, and
+ * the low part is bf16(x - bf16(x)) of them as well; nothing is flushed to zero.  aux != NULL: x is first multiplied by the
  * activation derivative at aux (act 1: ReLU with aux = forward output, 2: erf-GELU with aux = pre-activation; same
  * layout and leading dimension as x) - the backward of a fused Linear+activation without an fp32 intermediate.
  * SPLIT operands (precision mode "bf16s", the forward products): A16lo / B16lo (both or neither; same leading dimensions as
@@ -251,7 +257,8 @@ int spe_cvt_bf16_h(const float* x, long ldx, int R, int C, void* out, void* out_
  * Linear weight after an optimizer step).  jobs_dev: device array of njobs records of 64 bytes
  *   { const float* x; void* out; void* outT; long ldt; int R, C, tile0, tiles_c; void* out_lo; long flags; }     out, out_lo [R][C], outT [C][ldt], ldt >= R;
  * tiles_c = ceil(C/64), tile0 = running sum of tiles_c * ceil(max(R, ldt)/64) over the preceding jobs; total_tiles = that
- * sum over all jobs.  out, out_lo or outT may be NULL per job.  flags bit 0: out_lo receives IEEE fp16(x) instead of the low part. */
+ * sum over all jobs.  out, out_lo or outT may be NULL per job.  flags bit 0: out_lo receives IEEE fp16(x) instead of the low part.
+ * Alignment as for spe_cvt_bf16 with ldx = ldo = C: out / out_lo 8-byte aligned when C % 4 == 0, outT when ldt % 4 == 0. */
 int spe_cvt_bf16_multi(const void* jobs_dev, int njobs, int total_tiles, spe_stream_t stream);
 
 /* ---- masked softmax over scores[B,H,Nq,ld] (Nk valid columns per row).

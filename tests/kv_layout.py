@@ -4,6 +4,9 @@ spe_attn_pack_multi kinds 2 and 1), as index arithmetic on a token-major tensor 
   pack32: out[..., h, tile, st, lane, j] = x[..., tile*16 + (lane & 15), h, st*32 + (lane >> 4)*8 + j]      (32-wide steps)
   pack16: out[..., h, tile, dt, lane, j] = x[..., tile*16 + 4*(lane >> 4) + j, h, dt*16 + (lane & 15)]      (16-wide tiles)
 
+and of the record of the backbone score kernels (spe_attn_pack, spe_attn_pack_multi kind 32): pack32t, 32-wide steps plus one 16-wide
+tail step (see _index32t),
+
 with zeros where the token is >= S or the dim is >= D.  Elements are moved, never converted: any dtype (the tests pass raw 16-bit
 patterns as int16).  No project code is imported here."""
 import torch
@@ -64,6 +67,58 @@ def unpack32(frag, S, D):
 
 def unpack16(frag, S, D):
     return _unpack(frag, S, D, _index16)
+
+
+def frag_geom32t(D):
+    """(full, tail) of the kind-32 record: `full` 32-wide steps, then one 16-wide tail step when D % 32 is in 1 .. 16 (csrc/attn_pack.h:
+    frag_geom - a remainder of 17 .. 31 dims takes a whole 32-wide step instead)."""
+    rem = D % 32
+    return D // 32 + (1 if rem > 16 else 0), 1 if 0 < rem <= 16 else 0
+
+
+def record_elems32t(D):
+    full, tail = frag_geom32t(D)
+    return full * 512 + tail * 256
+
+
+def _index32t(S, D, device):
+    """Kind 32 (spe_attn_pack, spe_attn_pack_multi kind 32), restated from attn_pack_unit_t of csrc/attn_pack.h: the 8-byte unit u of a
+    record holds, for u < full * 128, step st = u >> 7, lane = (u & 127) >> 1 and dims st*32 + (lane >> 4)*8 + (u & 1)*4 + j - the first
+    `full` steps of pack32 - and beyond that lane = u - full*128 with dims full*32 + (lane >> 4)*4 + j; token tile*16 + (lane & 15) in both:
+      out[.., tile, st*512 + lane*8 + j]   = x[.., tile*16 + (lane & 15), h, st*32 + (lane >> 4)*8 + j]      (j < 8, st < full)
+      out[.., tile, full*512 + lane*4 + j] = x[.., tile*16 + (lane & 15), h, full*32 + (lane >> 4)*4 + j]    (j < 4, the tail step)"""
+    nt = (S + 15) // 16
+    full, tail = frag_geom32t(D)
+    e = torch.arange(full * 512 + tail * 256, device=device)
+    in_full = e < full * 512
+    st, lane_f, j_f = e // 512, (e % 512) // 8, e % 8
+    t = (e - full * 512).clamp(min=0)
+    lane_t, j_t = t // 4, t % 4
+    lane = torch.where(in_full, lane_f, lane_t)
+    dim = torch.where(in_full, st * 32 + (lane_f >> 4) * 8 + j_f, full * 32 + (lane_t >> 4) * 4 + j_t)
+    tile = torch.arange(nt, device=device).view(nt, 1)
+    tok = tile * 16 + (lane & 15).view(1, -1)
+    return tok, dim.view(1, -1).expand(nt, -1)
+
+
+def pack32t(x):
+    """x [..., S, H, D] -> kind-32 records [..., H, nt, record_elems32t(D)], zeros where the token is >= S or the dim is >= D."""
+    S, D = x.shape[-3], x.shape[-1]
+    tok, dim = _index32t(S, D, x.device)
+    valid = (tok < S) & (dim < D)
+    xh = x.movedim(-2, -3)
+    out = xh[..., tok.clamp(max=S - 1), dim.clamp(max=D - 1)]
+    return torch.where(valid, out, torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+def unpack32t(frag, S, D):
+    """-> (x [..., S, H, D], pad): pad = the record elements that belong to no (token, dim) of x."""
+    tok, dim = _index32t(S, D, frag.device)
+    assert frag.shape[-2:] == tok.shape, (frag.shape, tok.shape)
+    valid = (tok < S) & (dim < D)
+    xh = torch.zeros(frag.shape[:-2] + (S, D), dtype=frag.dtype, device=frag.device)
+    xh[..., tok[valid], dim[valid]] = frag[..., valid]
+    return xh.movedim(-3, -2), frag[..., ~valid]
 
 
 # the Tier-1 shapes (L, B, S, H, dh) of tests/test_decoder_kv_gpu.py; the last one is cfg2 (25 248 records: every wave of

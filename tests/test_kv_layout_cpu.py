@@ -41,6 +41,55 @@ def test_layout_formulas_by_hand():
         assert int(f16[h, tile, dt, lane, j]) == (int(x[tok, h, dim]) if tok < S and dim < D else 0)
 
 
+DH32T = (8, 16, 17, 24, 32, 33, 40, 48, 49, 64)
+N32T = (1, 15, 16, 17, 100)
+
+
+@pytest.mark.parametrize("dh", DH32T)
+def test_pack32t_identity_and_zero_padding(dh):
+    """The kind-32 record (32-wide steps + one 16-wide tail step): a bijection between the (token, dim) elements and their slots, zeros in
+    every other slot, at every head dim class of frag_geom and token counts around the 16-row tile."""
+    B, H = 2, 3
+    full, tail = kl.frag_geom32t(dh)
+    assert (full, tail) == {8: (0, 1), 16: (0, 1), 17: (1, 0), 24: (1, 0), 32: (1, 0), 33: (1, 1), 40: (1, 1), 48: (1, 1), 49: (2, 0), 64: (2, 0)}[dh]
+    for N in N32T:
+        g = torch.Generator().manual_seed(N * 131 + dh)
+        x = torch.randint(1, 32767, (B, N, H, dh), generator=g, dtype=torch.int16)
+        f = kl.pack32t(x)
+        assert f.shape == (B, H, (N + 15) // 16, full * 512 + tail * 256)
+        back, pad = kl.unpack32t(f, N, dh)
+        assert torch.equal(back, x)
+        assert pad.numel() == f.numel() - x.numel() and not pad.any()
+        assert int((f != 0).sum()) == x.numel()
+        # the full steps are those of pack32
+        p32 = kl.pack32(x)
+        assert torch.equal(f[..., :full * 512], p32[:, :, :, :full].reshape(B, H, (N + 15) // 16, full * 512))
+
+
+@pytest.mark.parametrize("dh", DH32T)
+def test_pack32t_record_size_is_the_librarys(dh):
+    from spe_amd import kernels as K
+    assert kl.record_elems32t(dh) == K.frag_record_elems(dh)
+
+
+def test_pack32t_formula_by_hand():
+    """Single elements spelled out from attn_pack_unit_t (8-byte unit u of a record -> lane, first dim), independent of _index32t."""
+    S, H, D = 21, 2, 40                                  # one full step + the tail step
+    x = torch.arange(1, S * H * D + 1, dtype=torch.int32).view(S, H, D)
+    f = kl.pack32t(x)
+    full = 1
+    for h, tile, u, j in [(0, 0, 0, 0), (1, 1, 127, 3), (0, 1, 77, 2), (1, 0, 128, 0), (0, 0, 128 + 17, 1), (1, 1, 128 + 40, 3), (0, 1, 191, 0)]:
+        if u < full * 128:
+            st, w = u >> 7, u & 127
+            ln = w >> 1
+            d0 = st * 32 + (ln >> 4) * 8 + (w & 1) * 4
+        else:
+            ln = u - full * 128
+            d0 = full * 32 + (ln >> 4) * 4
+        tok, dim = tile * 16 + (ln & 15), d0 + j
+        assert int(f[h, tile, u * 4 + j]) == (int(x[tok, h, dim]) if tok < S and dim < D else 0), (h, tile, u, j)
+
+
 def test_expected_frags_sources():
     """expected_frags reads k_content from block 2l of ym, v from block 2l + 1, k_pos from block l of yp, and honours wider rows."""
     L, B, S, H, dh = 2, 1, 3, 2, 8
