@@ -44,7 +44,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_gemm_f32_plan (the kernel selection and launch choices of spe_gemm_f32 / spe_gemm_ex, host only)
  * spe_jpeg_probe / _entropy / _reconstruct (baseline JPEG decoding: host entropy pass, device IDCT to RGB)
  * spe_adamw_flat_ema / spe_swap_flat (the weight EMA kept inside the optimizer's update launch, and its exchange with the parameters)
- * - 108 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
+ * spe_linear_small_plan (the launch choices of the spe_linear_small_* entries, host only)
+ * - 109 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -179,7 +180,11 @@ int spe_gemm_bf16nt(const void* A16, const void* B16, const void* A16lo, const v
  * spe_linear_small_bwd: dx [R][K] = dy' W, dW [N][K] = dy'^T x, db [N] = colsum(dy') in one grid, dy' = dy (fp32 [R][N]) times
  *   the derivative of the fused activation at aux (act 1: forward output, act 2: pre-activation; aux NULL: none); x16 [R][K] and
  *   WT16 [K][N] bf16; any of dx / dW / db may be NULL.  dW and db are OVERWRITTEN (no zeroing needed), db is summed in a fixed
- *   order (no atomics).  K, N multiples of 8, operands 16-B aligned; -2 otherwise. */
+ *   order (no atomics).
+ * Status -2 (nothing launched, nothing written) - forward: K <= 0 or no multiple of 8, ldx no multiple of 4, or x, W16, W16lo, x16_out not
+ *   16-B aligned; N, ldc, y, pre and bias are free (an unaligned y / pre or ldc % 4 != 0 takes 4-byte stores).  Backward: K or N no
+ *   multiple of 8; dy, aux, x16, WT16, dx or dW not 16-B aligned (db is free); dx without WT16, dW without x16, aux with an act other
+ *   than 1 or 2.  R or N <= 0 (backward: or K <= 0): status 0, nothing to do - as when none of dx / dW / db is asked for. */
 int spe_linear_small_fwd(const float* x, long ldx, const void* W16, const void* W16lo, const float* bias, float* y, float* pre,
                          void* x16_out, int R, int N, int K, long ldc, int act, spe_stream_t stream);
 int spe_linear_small_bwd(const float* dy, const float* aux, int act, const void* x16, const void* WT16, float* dx, float* dW,
@@ -196,8 +201,23 @@ int spe_linear_small_bwd(const float* dy, const float* aux, int act, const void*
  *   dW[i] / db[i] are not written.  dx, dW, db (or single elements of dW / db) may be NULL.  N % 128 == 0. */
 int spe_linear_small_group_fwd(const float* x, long ldx, const void* const* W16, const void* const* W16lo, const float* const* bias,
                                const float* const* add, float* const* y, void* x16_out, int R, int nblk, int N, int K, spe_stream_t stream);
+/* Status -2 of the group entries - both: nblk > 16, K <= 0 or no multiple of 8.  Forward: N % 32, ldx % 4, x / x16_out / W16[i] / W16lo[i] / y[i] / add[i] not
+ *   16-B aligned, a NULL W16[i] or y[i], a NULL W16lo[i] when W16lo is given (`bias` or single bias[i] may be NULL: no bias).  Backward:
+ *   N % 128, x16 / dx / dy[i] / WT16[i] / dW[i] not 16-B aligned, dx without WT16 or with a NULL WT16[i], dW without x16.  R, N or nblk <= 0
+ *   (backward: or K <= 0): status 0.  Backward with every dy[i] NULL: dx, if asked for, is all zeros, no dW / db is written. */
 int spe_linear_small_group_bwd(const float* const* dy, const void* x16, const void* const* WT16, float* dx, float* const* dW,
                                float* const* db, int R, int nblk, int N, int K, spe_stream_t stream);
+/* spe_linear_small_plan: the launch choices of the four entries above for a problem.  Host only: no device, no stream, nothing is launched;
+ * the entries fill their launch from the same function, so tests and tools can tell which kernel instance and which grid a shape takes.
+ * entry: 0 spe_linear_small_fwd, 1 _bwd, 2 _group_fwd, 3 _group_bwd; N is the width of ONE Linear, nblk and ldx are ignored where the
+ * entry has none; split: W16lo given; want_dx / want_dw / want_db: the outputs asked for (entry 1; entry 3 reads want_dx only); any_dw
+ * (entry 3): some output i has a dy[i] and a dW[i] or db[i].
+ * v[7] = { KC (contraction chunk of the k-contiguous programs: 384 or 128), RC (row chunk of the dW program: 512 or 256, 0 forward),
+ * SPLIT, tiles_dx, tiles_dw (workgroups of the two backward programs; 0 forward), grid.x, dynamic LDS bytes } - the instance is
+ * linear_small_fwd_kernel<KC, SPLIT> or linear_small_bwd_kernel<KC, RC>; all zero when there is nothing to do.  Returns the status the
+ * entry would return for these arguments, except for the parts of -2 that depend on pointers. */
+int spe_linear_small_plan(int entry, int R, int N, int K, int nblk, long ldx, int split, int want_dx, int want_dw, int want_db,
+                          int any_dw, long* v);
 /* spe_gemm_bf16tn: C[m][n] = alpha * sum_r A16[r][m] * B16[r][n] - the weight gradient dW = dy^T x of a Linear (autograd of
  * reference models/cait.py:376,390,409, models/transformer.py:368-425) on ROW-MAJOR bf16 operands A16 [R, lda] (M columns)
  * and B16 [R, ldb] (N columns): the contraction runs over rows, the MFMA operands are formed by LDS transpose reads

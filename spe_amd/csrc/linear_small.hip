@@ -309,108 +309,146 @@ static int ls_latency_tiles() {       // grids up to this many workgroups take t
     if (v < 0) v = SPE_KNOB("SPE_LS_WIDE_MAX", 320);
     return v;
 }
+static bool ls_group_kc_wide(int N) { return N % 384 == 0; }      // group backward: the dx chunks must not straddle two blocks
 
-// C-ABI: see include/spe_hip.h.  -2: unsupported shape / alignment (K, N multiples of 8; 16-B aligned operands; contiguous rows).
+// ---- the launch choices of the four entries, in ONE place (spe_linear_small_plan shows them; host only) -----------------------------------
+// entry: 0 spe_linear_small_fwd, 1 _bwd, 2 _group_fwd, 3 _group_bwd.  Everything that follows from the shape alone is decided here: the
+// shape part of status -2, "nothing to do", the kernel instance (kc, rc, split), the two tile counts, the grid and the dynamic LDS bytes.
+// What depends on pointers (16-byte alignment, NULL combinations, the elements of the group tables) stays with the entries.
+struct LsPlan { int kc, rc, split, tiles_dx, tiles_dw, grid, smem; };
+static int ls_smem_fwd(int kc, bool split) { return (split ? 4 : 2) * LS_T * (kc + 8) * (int)sizeof(unsigned short); }
+static int ls_smem_bwd(int kc, int rc) { const int a = 2 * LS_T * (kc + 8) * 2, b = 2 * rc * LS_LDT * 2 + 32 * 32 * 4; return a > b ? a : b; }
+static int ls_plan(int entry, int R, int N, int K, int nblk, long ldx, bool split, bool want_dx, bool want_dw, bool want_db, bool any_dw,
+                   LsPlan& pl) {
+    pl = LsPlan{};
+    if (entry < 0 || entry > 3) return -2;
+    const bool fwd = entry == 0 || entry == 2, group = entry >= 2;
+    // nothing to do: status 0 before any other check (the forward entries do not look at K for it)
+    if (R <= 0 || N <= 0 || (!fwd && K <= 0) || (group && nblk <= 0)) return 0;
+    if (group && nblk > LS_MAXBLK) return -2;
+    if (K <= 0 || (K & 7)) return -2;
+    if (fwd && (ldx & 3)) return -2;
+    if (entry == 1 && (N & 7)) return -2;
+    if (entry == 2 && (N % LS_T)) return -2;
+    if (entry == 3 && (N % 128)) return -2;
+    const int tr = (R + LS_T - 1) / LS_T, tk = (K + LS_T - 1) / LS_T;
+    const int tn = group ? nblk * N / LS_T : (N + LS_T - 1) / LS_T;
+    if (fwd) {
+        pl.grid = tr * tn;
+        pl.split = split;
+        pl.kc = pl.grid <= ls_latency_tiles() ? 384 : 128;
+        pl.smem = ls_smem_fwd(pl.kc, split);
+        return 0;
+    }
+    pl.tiles_dx = want_dx ? tr * tk : 0;
+    if (group) pl.tiles_dw = any_dw ? tn * tk : 0;
+    else pl.tiles_dw = want_dw ? tn * tk : (want_db ? tn : 0);          // bias gradient only: the k-tile-0 workgroups
+    pl.grid = pl.tiles_dx + pl.tiles_dw;
+    if (pl.grid == 0) return 0;
+    const bool wide = (!group || ls_group_kc_wide(N)) && pl.grid <= ls_latency_tiles();
+    pl.kc = wide ? 384 : 128; pl.rc = wide ? 512 : 256;
+    pl.smem = ls_smem_bwd(pl.kc, pl.rc);
+    return 0;
+}
+
+// C-ABI: see include/spe_hip.h
+extern "C" int spe_linear_small_plan(int entry, int R, int N, int K, int nblk, long ldx, int split, int want_dx, int want_dw, int want_db,
+                                     int any_dw, long* v) {
+    LsPlan pl;
+    const int st = ls_plan(entry, R, N, K, nblk, ldx, split != 0, want_dx != 0, want_dw != 0, want_db != 0, any_dw != 0, pl);
+    v[0] = pl.kc; v[1] = pl.rc; v[2] = pl.split; v[3] = pl.tiles_dx; v[4] = pl.tiles_dw; v[5] = pl.grid; v[6] = pl.smem;
+    return st;
+}
+
+// the one launch of a planned forward / backward: the instance is the plan's (kc, split) / (kc, rc)
+static int ls_launch_fwd(const LsPlan& pl, const LinSmallArgs& p, hipStream_t stream) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_small_fwd_kernel<384, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           ls_smem_fwd(384, true));
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+    if (pl.kc == 384) {
+        if (pl.split) hipLaunchKernelGGL((linear_small_fwd_kernel<384, true>), dim3(pl.grid), dim3(256), pl.smem, stream, p);
+        else hipLaunchKernelGGL((linear_small_fwd_kernel<384, false>), dim3(pl.grid), dim3(256), pl.smem, stream, p);
+    } else {
+        if (pl.split) hipLaunchKernelGGL((linear_small_fwd_kernel<128, true>), dim3(pl.grid), dim3(256), pl.smem, stream, p);
+        else hipLaunchKernelGGL((linear_small_fwd_kernel<128, false>), dim3(pl.grid), dim3(256), pl.smem, stream, p);
+    }
+    SPE_CHECK_LAUNCH();
+    return 0;
+}
+static int ls_launch_bwd(const LsPlan& pl, const LinSmallArgs& p, hipStream_t stream) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_small_bwd_kernel<384, 512>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           ls_smem_bwd(384, 512));
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+    if (pl.kc == 384) hipLaunchKernelGGL((linear_small_bwd_kernel<384, 512>), dim3(pl.grid), dim3(256), pl.smem, stream, p);
+    else hipLaunchKernelGGL((linear_small_bwd_kernel<128, 256>), dim3(pl.grid), dim3(256), pl.smem, stream, p);
+    SPE_CHECK_LAUNCH();
+    return 0;
+}
+
+// C-ABI: see include/spe_hip.h.  -2: unsupported shape (ls_plan) / alignment / NULL combination (here).
 extern "C" int spe_linear_small_fwd(const float* x, long ldx, const void* W16, const void* W16lo, const float* bias, float* y, float* pre,
                                     void* x16_out, int R, int N, int K, long ldc, int act, hipStream_t stream) {
-    if (R <= 0 || N <= 0) return 0;
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (K <= 0 || (K & 7) || (ldx & 3) || !al16(x) || !al16(W16) || !al16(W16lo) || !al16(x16_out)) return -2;
+    LsPlan pl;
+    const int st = ls_plan(0, R, N, K, 0, ldx, W16lo != nullptr, false, false, false, false, pl);
+    if (st || pl.grid == 0) return st;
+    if (!al16(x) || !al16(W16) || !al16(W16lo) || !al16(x16_out)) return -2;
     LinSmallArgs p = {};
     p.g.B = reinterpret_cast<const unsigned short*>(W16); p.g.Blo = reinterpret_cast<const unsigned short*>(W16lo);
     p.g.C = y; p.g.C2 = pre; p.g.bias = bias; p.g.M = R; p.g.N = N; p.g.K = K; p.g.ldc = ldc; p.g.alpha = 1.f; p.g.act = act; p.g.splitk = 1;
     p.x = x; p.ldx = ldx; p.x16 = reinterpret_cast<unsigned short*>(x16_out);
-    const int tiles = ((R + LS_T - 1) / LS_T) * ((N + LS_T - 1) / LS_T);
-    const bool split = W16lo != nullptr;
-    const bool wide = tiles <= ls_latency_tiles();
-    const int smem = (split ? 4 : 2) * LS_T * ((wide ? 384 : 128) + 8) * (int)sizeof(unsigned short);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_small_fwd_kernel<384, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           4 * LS_T * 392 * (int)sizeof(unsigned short));
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    if (wide) {
-        if (split) hipLaunchKernelGGL((linear_small_fwd_kernel<384, true>), dim3(tiles), dim3(256), smem, stream, p);
-        else hipLaunchKernelGGL((linear_small_fwd_kernel<384, false>), dim3(tiles), dim3(256), smem, stream, p);
-    } else {
-        if (split) hipLaunchKernelGGL((linear_small_fwd_kernel<128, true>), dim3(tiles), dim3(256), smem, stream, p);
-        else hipLaunchKernelGGL((linear_small_fwd_kernel<128, false>), dim3(tiles), dim3(256), smem, stream, p);
-    }
-    SPE_CHECK_LAUNCH();
-    return 0;
+    return ls_launch_fwd(pl, p, stream);
 }
 
 extern "C" int spe_linear_small_bwd(const float* dy, const float* aux, int act, const void* x16, const void* WT16, float* dx, float* dW,
                                     float* db, int R, int N, int K, hipStream_t stream) {
     if (R <= 0 || N <= 0 || K <= 0) return 0;
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if ((K & 7) || (N & 7) || !al16(dy) || !al16(aux) || !al16(x16) || !al16(WT16) || !al16(dx) || !al16(dW)) return -2;
+    LsPlan pl;
+    const int st = ls_plan(1, R, N, K, 0, 0, false, dx != nullptr, dW != nullptr, db != nullptr, false, pl);
+    if (st) return st;
+    if (!al16(dy) || !al16(aux) || !al16(x16) || !al16(WT16) || !al16(dx) || !al16(dW)) return -2;
     if ((dx && !WT16) || (dW && !x16) || (aux && act != 1 && act != 2)) return -2;
+    if (pl.grid == 0) return 0;           // nothing wanted
     LinSmallArgs p = {};
     p.x = dy; p.aux = aux; p.act = act; p.xs16 = reinterpret_cast<const unsigned short*>(x16);
     p.g.B = reinterpret_cast<const unsigned short*>(WT16); p.g.C = dx;
     p.dW = dW; p.db = db; p.R = R; p.N = N; p.K = K;
-    const int tr = (R + LS_T - 1) / LS_T, tk = (K + LS_T - 1) / LS_T, tn = (N + LS_T - 1) / LS_T;
-    p.tiles_dx = dx ? tr * tk : 0;
-    const int tiles_dw = dW ? tn * tk : (db ? tn : 0);          // bias gradient only: the k-tile-0 workgroups
-    if (p.tiles_dx + tiles_dw == 0) return 0;
-    const bool wide = p.tiles_dx + tiles_dw <= ls_latency_tiles();
-    auto smem_of = [](int kc, int rc) { const int a = 2 * LS_T * (kc + 8) * 2, b = 2 * rc * LS_LDT * 2 + 32 * 32 * 4; return a > b ? a : b; };
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_small_bwd_kernel<384, 512>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           smem_of(384, 512));
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    if (wide) hipLaunchKernelGGL((linear_small_bwd_kernel<384, 512>), dim3(p.tiles_dx + tiles_dw), dim3(256), smem_of(384, 512), stream, p);
-    else hipLaunchKernelGGL((linear_small_bwd_kernel<128, 256>), dim3(p.tiles_dx + tiles_dw), dim3(256), smem_of(128, 256), stream, p);
-    SPE_CHECK_LAUNCH();
-    return 0;
+    p.tiles_dx = pl.tiles_dx;
+    return ls_launch_bwd(pl, p, stream);
 }
 
 // ---- group entries: nblk Linears of equal shape [N, K] on ONE input (the decoder's query-side projections: reference models/transformer.py:
 // 368-372 sa_qcontent / sa_kcontent / sa_v of tgt, 369-371 + 399 sa_qpos / sa_kpos / ca_qpos of query_pos for every layer) - one launch each way
 // for all of them, every Linear keeping its own weight copies, output and gradient buffers (pointer tables, nothing is stacked).
-static bool ls_group_kc_wide(int N) { return N % 384 == 0; }
 extern "C" int spe_linear_small_group_fwd(const float* x, long ldx, const void* const* W16, const void* const* W16lo, const float* const* bias,
                                           const float* const* add, float* const* y, void* x16_out, int R, int nblk, int N, int K, hipStream_t stream) {
-    if (R <= 0 || N <= 0 || nblk <= 0) return 0;
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (nblk > LS_MAXBLK || K <= 0 || (K & 7) || (N % LS_T) || (ldx & 3) || !al16(x) || !al16(x16_out)) return -2;
-    LinSmallArgs p = {};
     const bool split = W16lo != nullptr;
+    LsPlan pl;
+    const int st = ls_plan(2, R, N, K, nblk, ldx, split, false, false, false, false, pl);
+    if (st || pl.grid == 0) return st;
+    if (!al16(x) || !al16(x16_out)) return -2;
+    LinSmallArgs p = {};
     for (int i = 0; i < nblk; ++i) {
         if (!W16[i] || !y[i] || !al16(W16[i]) || !al16(y[i]) || (split && (!W16lo[i] || !al16(W16lo[i])))) return -2;
         p.Wb[i] = reinterpret_cast<const unsigned short*>(W16[i]); p.Wlob[i] = split ? reinterpret_cast<const unsigned short*>(W16lo[i]) : nullptr;
         p.biasb[i] = bias ? bias[i] : nullptr; p.yb[i] = y[i];
         p.addb[i] = add ? add[i] : nullptr;
-        if (p.addb[i] && (!al16(p.addb[i]) || (N & 3))) return -2;
+        if (p.addb[i] && !al16(p.addb[i])) return -2;           // N % 32 == 0: its rows are whole float4s
     }
     p.nblk = nblk; p.Nblk = N;
     p.g.M = R; p.g.N = nblk * N; p.g.K = K; p.g.ldc = N; p.g.alpha = 1.f; p.g.act = 0; p.g.splitk = 1;
     p.x = x; p.ldx = ldx; p.x16 = reinterpret_cast<unsigned short*>(x16_out);
-    const int tiles = ((R + LS_T - 1) / LS_T) * (nblk * N / LS_T);
-    const bool wide = tiles <= ls_latency_tiles();
-    const int smem = (split ? 4 : 2) * LS_T * ((wide ? 384 : 128) + 8) * (int)sizeof(unsigned short);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_small_fwd_kernel<384, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           4 * LS_T * 392 * (int)sizeof(unsigned short));
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    if (wide) {
-        if (split) hipLaunchKernelGGL((linear_small_fwd_kernel<384, true>), dim3(tiles), dim3(256), smem, stream, p);
-        else hipLaunchKernelGGL((linear_small_fwd_kernel<384, false>), dim3(tiles), dim3(256), smem, stream, p);
-    } else {
-        if (split) hipLaunchKernelGGL((linear_small_fwd_kernel<128, true>), dim3(tiles), dim3(256), smem, stream, p);
-        else hipLaunchKernelGGL((linear_small_fwd_kernel<128, false>), dim3(tiles), dim3(256), smem, stream, p);
-    }
-    SPE_CHECK_LAUNCH();
-    return 0;
+    return ls_launch_fwd(pl, p, stream);
 }
 
 // dx [R][K] = sum_i dy_i W_i, dW_i [N][K] = dy_i^T x, db_i [N] = colsum(dy_i); dy[i] NULL: that output received no gradient (its dW / db are
@@ -419,7 +457,10 @@ extern "C" int spe_linear_small_group_bwd(const float* const* dy, const void* x1
                                           float* const* db, int R, int nblk, int N, int K, hipStream_t stream) {
     if (R <= 0 || N <= 0 || K <= 0 || nblk <= 0) return 0;
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (nblk > LS_MAXBLK || (K & 7) || (N % 128) || !al16(x16) || !al16(dx) || (dx && !WT16) || (dW && !x16)) return -2;
+    LsPlan pl;
+    int st = ls_plan(3, R, N, K, nblk, 0, false, dx != nullptr, false, false, true, pl);      // the status alone: the tables are read after it
+    if (st) return st;
+    if (!al16(x16) || !al16(dx) || (dx && !WT16) || (dW && !x16)) return -2;
     LinSmallArgs p = {};
     bool any_dw = false;
     for (int i = 0; i < nblk; ++i) {
@@ -428,24 +469,11 @@ extern "C" int spe_linear_small_group_bwd(const float* const* dy, const void* x1
         if (!al16(p.dyb[i]) || !al16(p.WTb[i]) || !al16(p.dWb[i]) || (dx && !p.WTb[i])) return -2;
         any_dw = any_dw || (p.dyb[i] && (p.dWb[i] || p.dbb[i]));
     }
+    st = ls_plan(3, R, N, K, nblk, 0, false, dx != nullptr, false, false, any_dw, pl);
+    if (st || pl.grid == 0) return st;
     p.nblk = nblk; p.Nblk = N;
     p.xs16 = reinterpret_cast<const unsigned short*>(x16); p.g.C = dx;
     p.R = R; p.N = nblk * N; p.K = K;
-    const int tr = (R + LS_T - 1) / LS_T, tk = (K + LS_T - 1) / LS_T, tn = nblk * N / LS_T;
-    p.tiles_dx = dx ? tr * tk : 0;
-    const int tiles_dw = any_dw ? tn * tk : 0;
-    if (p.tiles_dx + tiles_dw == 0) return 0;
-    const bool wide = ls_group_kc_wide(N) && p.tiles_dx + tiles_dw <= ls_latency_tiles();
-    auto smem_of = [](int kc, int rc) { const int a = 2 * LS_T * (kc + 8) * 2, b = 2 * rc * LS_LDT * 2 + 32 * 32 * 4; return a > b ? a : b; };
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_small_bwd_kernel<384, 512>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           smem_of(384, 512));
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    if (wide) hipLaunchKernelGGL((linear_small_bwd_kernel<384, 512>), dim3(p.tiles_dx + tiles_dw), dim3(256), smem_of(384, 512), stream, p);
-    else hipLaunchKernelGGL((linear_small_bwd_kernel<128, 256>), dim3(p.tiles_dx + tiles_dw), dim3(256), smem_of(128, 256), stream, p);
-    SPE_CHECK_LAUNCH();
-    return 0;
+    p.tiles_dx = pl.tiles_dx;
+    return ls_launch_bwd(pl, p, stream);
 }

@@ -367,6 +367,25 @@ def _lin_small_ok(R, N, K):
     return LINEAR16 and _PRECISION != 1 and LINEAR16_MIN_ROWS <= R < LINEAR_SMALL_MAX_ROWS and N % 8 == 0 and K % 8 == 0
 
 
+LINEAR_SMALL_PLAN_FIELDS = ("KC", "RC", "SPLIT", "tiles_dx", "tiles_dw", "grid_x", "lds_bytes")
+LINEAR_SMALL_ENTRIES = ("fwd", "bwd", "group_fwd", "group_bwd")
+
+
+def linear_small_plan(entry, R, N, K, nblk=0, ldx=None, split=False, dx=False, dW=False, db=False, any_dw=False):
+    """The launch choices of spe_linear_small_<entry> (entry in LINEAR_SMALL_ENTRIES) for a problem (spe_linear_small_plan, the
+    launchers' own function): dict(KC, RC, SPLIT, tiles_dx, tiles_dw, grid_x, lds_bytes, status) - linear_small_fwd_kernel<KC, SPLIT> or
+    linear_small_bwd_kernel<KC, RC>, the workgroups of the dx and of the dW / db program, grid.x, the dynamic LDS bytes and the status the
+    entry would return (its pointer checks aside); all zero when nothing would be launched.  N: the width of one Linear; split: a low
+    weight part is given; dx / dW / db: the outputs asked for; any_dw (group_bwd): some output has a dy and a dW or db.  Needs no device.
+    For tests and tools: no hot path calls it."""
+    v = (ctypes.c_long * len(LINEAR_SMALL_PLAN_FIELDS))()
+    rc = lib.load().spe_linear_small_plan(LINEAR_SMALL_ENTRIES.index(entry), R, N, K, nblk, K if ldx is None else ldx, int(split),
+                                          int(dx), int(dW), int(db), int(any_dw), v)
+    out = dict(zip(LINEAR_SMALL_PLAN_FIELDS, (int(x) for x in v)))
+    out["status"] = rc
+    return out
+
+
 def _lin16_ok(R, N, K):
     return LINEAR16 and _PRECISION != 1 and R >= LINEAR16_MIN_ROWS and N % 8 == 0 and K % 8 == 0
 
