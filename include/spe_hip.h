@@ -45,7 +45,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_jpeg_probe / _entropy / _reconstruct (baseline JPEG decoding: host entropy pass, device IDCT to RGB)
  * spe_adamw_flat_ema / spe_swap_flat (the weight EMA kept inside the optimizer's update launch, and its exchange with the parameters)
  * spe_linear_small_plan (the launch choices of the spe_linear_small_* entries, host only)
- * - 109 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
+ * spe_grad_report (per-parameter gradient and weight statistics on the flat buckets, gated on the guard block: what a skipped step skipped)
+ * - 110 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -869,6 +870,44 @@ int spe_adamw_flat_ema(float* p, float* g, float* m, float* v, float* e, long n,
                        const float* partials, int npartials, float max_norm, int write_grad, float grad_scale,
                        const void* guard, double decay, int warmup, long t, spe_stream_t stream);
 int spe_swap_flat(float* a, float* b, long n, spe_stream_t stream);
+
+/* ---- per-parameter gradient report on the flat buckets (no reference site: the reference exits on a non-finite loss, engine.py:147-159,
+ * and logs no per-layer norms).  The guarded step can only count its skips; this entry says which parameter carried the NaN, the
+ * infinity or the finite element whose square overflows, and gives the gradient / weight norms of every parameter.
+ * g, p: the flat gradient and parameter buffers of one bucket, n elements each, 16-B aligned; p may be NULL.  par_beg / par_len: device
+ * tables of npar entries, parameter i is g[par_beg[i] .. par_beg[i] + par_len[i]) (and the same range of p); what lies between the
+ * parameters is never read.  The table contents are TRUSTED, as seg_end of spe_adamw_flat is: ranges inside [0, n), par_len < 2^31.
+ * A parameter may start anywhere (one that does not start on a 16-B boundary is read with 4-B loads: same values, same record).
+ * out: npar records of SPE_GRAD_REPORT_WORDS 4-byte words, 16-B aligned:
+ *   fp32  [0] sum of (grad_scale * g)^2 over the finite elements of g   [1] max |grad_scale * g| over them (0 if there are none)
+ *         [2] sum of p^2   [3] max |p| (a NaN in p is ignored by the maximum and makes [2] NaN)      - both 0 with p == NULL
+ *   int32 [4] NaN elements of g   [5] +-inf elements of g   [6] index within the parameter (row-major) of the first non-finite element
+ *         of g, -1 if none   [7] the attempt index at the time of writing: guard words [0] + [1]; 0 with guard == NULL
+ * Arithmetic: fp32 throughout, every operation rounded on its own (no FMA, no fp64): s = grad_scale * g, q = s * s, then additions.  A
+ * finite element beyond ~1.8e19 therefore shows in [0] as inf, exactly as it overflows the guard's norm.  A non-finite element of g is
+ * counted and then taken as +0.0: the record is, bit for bit, that of the same tensor with those elements replaced by +0.0.
+ * grad_scale is finite.
+ * Order of the two sums of a parameter of L elements (x_j = q of element j, +0.0 for j >= L).  The parameter is cut into chunks of
+ * 16384 elements counted from its own first element; chunk c (elements 16384 c ...) is summed by one workgroup of T = 256 lanes:
+ *   1. vector v = 0, 1, ... of the chunk holds its elements 4v .. 4v + 3 and is reduced to   y_v = (x_4v + x_4v+1) + (x_4v+2 + x_4v+3);
+ *   2. lane t adds its vectors in ascending order:   a_t = ((0 + y_t) + y_(t+T)) + y_(t+2T) + ...   (pass k covers the chunk's
+ *      elements 1024 k .. 1024 k + 1023; 16 passes at most);
+ *   3. inside each wave of 64 consecutive lanes, six xor-butterfly steps   a_t <- a_t + a_(t xor o),  o = 32, 16, 8, 4, 2, 1;
+ *      every lane of the wave ends with the same bits;
+ *   4. the 4 wave sums are added in ascending wave order starting from 0:   P_c = (((0 + w_0) + w_1) + w_2) + w_3;
+ * and a second launch adds the chunk sums in ascending chunk order starting from 0:   ((0 + P_0) + P_1) + ...
+ * The record is thus a pure function of the parameter's values and length: it does not depend on par_beg, npar, n or the other
+ * parameters.  Maxima, counts and the first index are exact and order-free.  No atomics; one lane stores a record as two 16-B words.
+ * The chunk records pass through the reduction workspace (spe_set_reduce_workspace; 32 bytes for each of n / 16384 + npar slots) from
+ * the first launch to the second: launches must be stream-ordered, as for every user of that workspace.
+ * when: gating on the guard block of spe_adamw_gate - 0: always write (guard may be NULL); 1: write only if guard [3] (apply) is 0,
+ * i.e. this step is skipped; 2: only if apply == 0 and guard [1] (skipped) is 1, the first skipped step.  A workgroup that finds the
+ * condition false returns after reading the guard words and nothing else: out keeps every bit.
+ * -2: g or out NULL or not 16-B aligned, p or guard not 16-B aligned, a table NULL, npar < 1, when outside 0..2, when != 0 with
+ * guard NULL.  -4: no reduction workspace registered, or too small for the slots.  n <= 0: status 0, nothing launched. */
+#define SPE_GRAD_REPORT_WORDS 8
+int spe_grad_report(const float* g, const float* p, long n, const long* par_beg, const long* par_len, int npar,
+                    float grad_scale, const void* guard, int when, void* out, spe_stream_t stream);
 
 /* ---- diagnostic (never launched by the product): keep nwg workgroups resident for `micros` microseconds, streaming copies
  * through buf (buf_floats floats, 16-B aligned; NULL: idle spinning) - the one-GPU proxy for the CU / HBM share of an RCCL ring

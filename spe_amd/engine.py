@@ -69,6 +69,28 @@ def get_refinements_pseudo_label(outputs, samples, targets, args, postprocessors
     return targets_refine
 
 
+def format_skip_report(report, limit=5):
+    """One line from FlatAdamW.skip_report(): the attempt and up to `limit` parameters behind the skipped step - `name[index] nan=N inf=M`
+    for a parameter with non-finite elements (the index of the first), `name |g|max=X (square overflows fp32)` for one whose finite
+    elements overflow its own squared norm; without any culprit, the rows of largest |g| (only the total norm overflowed).  Pure host
+    code: no device access."""
+    def index(row):
+        return "[" + ", ".join(str(i) for i in row["first_bad"]) + "]" if row["first_bad"] is not None else ""
+
+    def tail(rows):
+        return f" (+{len(rows) - limit} more)" if len(rows) > limit else ""
+
+    head = f"Skipped step {report['attempt']}: "
+    culprits = report["culprits"]
+    if culprits:
+        parts = [f"{r['name']}{index(r)} nan={r['nan']} inf={r['inf']}" if r["nan"] + r["inf"] > 0
+                 else f"{r['name']} |g|max={r['grad_absmax']:.4g} (square overflows fp32)" for r in culprits[:limit]]
+        return head + "; ".join(parts) + tail(culprits)
+    largest = report["largest"]
+    parts = [f"{r['name']} |g|max={r['grad_absmax']:.4g}" for r in largest[:limit]]
+    return head + "no single parameter is non-finite, only the total squared norm overflows fp32; largest gradients: " + "; ".join(parts) + tail(largest)
+
+
 def apply_curriculum_coco(weight_dict, epoch):
     """engine.py:573-581, the COCO loop's curriculum: before epoch 1 only the image-label keys keep their weight.  The reference's
     second block (:578-581) zeroes the keys that contain `header` - there the LOG header string '[<time>] => Epoch: [<n>]', not
@@ -129,7 +151,11 @@ def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, devic
         print(f"Dropped the last {left} micro-batch(es) of the epoch: an incomplete accumulation cycle of {optimizer.reducer.accum_steps}")
     if flat and optimizer.skip_nonfinite and optimizer.skipped_steps() > 0:
         print(f"Optimizer steps skipped on a non-finite gradient: {optimizer.skipped_steps()} so far, the first at step {optimizer.first_skipped()}")
-    stats = ledger.global_avg()                  # synchronised between the ranks; raises if a step's total was not finite
+        if optimizer.skip_report_mode is not None:
+            report = optimizer.skip_report(model)
+            if report is not None:
+                print(format_skip_report(report))
+    stats = ledger.global_avg()                 # synchronised between the ranks; raises if a step's total was not finite
     print("Averaged stats:", ledger)
     return stats
 

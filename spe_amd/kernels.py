@@ -1678,6 +1678,28 @@ def adamw_flat_ema(p, g, m, v, e, seg_end_i64, seg_lr, seg_wd, beta1, beta2, eps
           float(max_norm), int(bool(write_grad)), float(grad_scale), _p(guard_i32), float(decay), int(bool(warmup)), int(t), _st())
 
 
+GRAD_REPORT_WORDS = 8             # SPE_GRAD_REPORT_WORDS of include/spe_hip.h
+# a record's words: fp32 0..3, int32 4..7
+REPORT_GRAD_SQ, REPORT_GRAD_ABSMAX, REPORT_WEIGHT_SQ, REPORT_WEIGHT_ABSMAX, REPORT_NAN, REPORT_INF, REPORT_FIRST_BAD, REPORT_ATTEMPT = range(8)
+
+
+def grad_report(g, p, par_beg, par_len, grad_scale, out, guard_i32=None, when=0):
+    """One record of GRAD_REPORT_WORDS words per parameter of a flat bucket into out (int32 [npar, 8]): gradient / weight squared norms
+    and maxima, NaN / inf counts, the first non-finite index, the attempt (spe_grad_report).  p may be None.  when 0: always; 1: only
+    if the guard block says this step is skipped; 2: only on the first skipped step - otherwise out keeps its bits."""
+    _chk(g, p)
+    npar = par_beg.numel()
+    if par_beg.dtype != torch.int64 or par_len.dtype != torch.int64 or par_len.numel() != npar:
+        raise ValueError("grad_report: par_beg and par_len are int64 tables of equal length")
+    if out.dtype != torch.int32 or out.numel() != npar * GRAD_REPORT_WORDS or not out.is_contiguous():
+        raise ValueError("grad_report: out is a contiguous int32 tensor of GRAD_REPORT_WORDS words per parameter")
+    if p is not None and p.numel() != g.numel():
+        raise ValueError("grad_report: g and p must have the same number of elements")
+    _call("spe_grad_report", _p(g), _p(p), g.numel(), _p(par_beg), _p(par_len), npar, float(grad_scale), _p(guard_i32), int(when),
+          _p(out), _st())
+    return out
+
+
 def swap_flat(a, b):
     """Exchange the bits of two flat fp32 buffers of equal size (spe_swap_flat)."""
     _chk(a, b)

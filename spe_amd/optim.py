@@ -16,8 +16,14 @@ untouched when it is not (see the class docstring).
 
 FlatAdamW(..., ema_decay=d) keeps an exponential moving average of the weights as one more flat fp32 buffer per bucket, updated by the
 update launch itself; `with optimizer.ema_weights():` swaps it into the parameters for an evaluation (see the class docstring).
+
+FlatAdamW(..., skip_nonfinite=True, skip_report="first" | "last") makes the guard's decision explainable: one gated spe_grad_report per bucket
+(csrc/grad_report.hip) writes, on a skipped step only, a record per parameter - NaN / inf counts, the first bad index, squared norm and
+largest magnitude of the gradient, the weight norm - and skip_report() reads it on the host afterwards.  grad_stats() is the same table
+on demand (per-layer gradient / weight norms for logging).
 """
 import contextlib
+import math
 
 import torch
 
@@ -57,12 +63,29 @@ class FlatAdamW(torch.optim.Optimizer):
     * `with optimizer.ema_weights(): evaluate(...)` exchanges parameters and EMA on entry and again on exit (one spe_swap_flat per
       bucket, cached 16-bit operand copies invalidated both times).  Inside the block step(), ema_reset(), ema_state_dict(),
       load_ema_state_dict() and a second ema_weights() raise RuntimeError.
-    * ema_reset(): see there - needed when model weights are loaded after the optimizer was built."""
+    * ema_reset(): see there - needed when model weights are loaded after the optimizer was built.
+
+    skip_report="first" | "last" (None: off, nothing allocated, step() issues the launches it issues without it; needs skip_nonfinite):
+    after the gate and before the update launches, step() issues one spe_grad_report per bucket, gated on the guard block - on an applied
+    step every workgroup returns after reading the guard words; on a skipped step ("first": on the first skipped step of the run only,
+    "last": on every skipped one, the latest overwrites) it writes one record per parameter from the buckets the skipped update then
+    leaves untouched.  step() still reads nothing back; skip_report() is the host read, grad_stats() the same table on demand.
+    What the report cannot resolve:
+    * Gradient accumulation: it sees the accumulated sum of the cycle, not the micro-batch that poisoned it.
+    * Several ranks: the buckets are identical on every rank after the all-reduce, so every rank holds the same report without a
+      collective - and none can say which rank produced the value.
+    * The records square grad_scale * g, the guard's norm squares g before it scales: with grad_scale < 1 an element in
+      (1.8e19, 1.8e19 / grad_scale) skips the step without an infinite grad_sq of its own; such a step reads as a total overflow
+      (below) with that parameter on top of "largest"."""
 
     def __init__(self, params, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
-                 write_clipped_grads=True, skip_nonfinite=False, ema_decay=None, ema_warmup=True):
+                 write_clipped_grads=True, skip_nonfinite=False, ema_decay=None, ema_warmup=True, skip_report=None):
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:          # NaN fails the comparison too
             raise ValueError(f"FlatAdamW: ema_decay must be None or in [0, 1), got {ema_decay}")
+        if skip_report not in (None, "first", "last"):
+            raise ValueError(f"FlatAdamW: skip_report must be None, 'first' or 'last', got {skip_report!r}")
+        if skip_report is not None and not skip_nonfinite:
+            raise ValueError("FlatAdamW: skip_report needs skip_nonfinite=True (it reports what the guard skipped)")
         if not getattr(reducer, "flatten_params", False):
             raise ValueError("FlatAdamW needs GradAllReducer(..., flatten_params=True)")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -99,6 +122,7 @@ class FlatAdamW(torch.optim.Optimizer):
         self.ema_warmup = bool(ema_warmup)
         self._ema_swapped = False
         self._ema_views = {}
+        self.skip_report_mode = skip_report          # (the method skip_report() is the host read)
         self._buckets = []
         for b in reducer.buckets:
             n = b["flat"].numel()
@@ -124,7 +148,12 @@ class FlatAdamW(torch.optim.Optimizer):
             if len(ends) > 64:
                 raise ValueError("FlatAdamW: more than 64 parameter-group runs in one bucket")
             self._buckets.append({"b": b, "m": m, "v": v, "ema": ema, "groups": groups,
-                                  "seg_end": host_to_device(ends, torch.int64, m.device), "tab": None, "tab_key": None})
+                                  "seg_end": host_to_device(ends, torch.int64, m.device), "tab": None, "tab_key": None,
+                                  "par_tab": None, "report": None, "stats": None})
+            if skip_report is not None:
+                e = self._buckets[-1]
+                e["par_tab"] = self._par_tables(e)
+                e["report"] = torch.zeros((len(offs), K.GRAD_REPORT_WORDS), device=dev, dtype=torch.int32)
         self._partials = torch.zeros((_NORM_BLOCKS * len(self._buckets),), device=dev, dtype=torch.float32)
         if self.ema_decay is not None:
             self.ema_reset()
@@ -152,6 +181,11 @@ class FlatAdamW(torch.optim.Optimizer):
                 K.sqnorm_partials(e["b"]["flat"], self._partials[i * _NORM_BLOCKS:(i + 1) * _NORM_BLOCKS])
         if guarded:
             K.adamw_gate(self._guard, self._partials, clip, self.reducer.grad_scale(), b1, b2)
+            if self.skip_report_mode is not None:          # gated on the block the gate has just written: returns at once on an applied step
+                when = 2 if self.skip_report_mode == "first" else 1
+                for e in self._buckets:
+                    K.grad_report(e["b"]["flat"], e["b"]["flat_p"], e["par_tab"][0], e["par_tab"][1], self.reducer.grad_scale(),
+                                  e["report"], guard_i32=self._guard, when=when)
         for e in self._buckets:
             key = tuple((self.param_groups[g]["lr"], self.param_groups[g]["weight_decay"]) for g in e["groups"])
             if key != e["tab_key"]:            # LR scheduler moved: refresh the (tiny) per-segment table
@@ -235,6 +269,79 @@ class FlatAdamW(torch.optim.Optimizer):
         finally:
             self._ema_swap()
             self._ema_swapped = False
+
+    # ---- gradient report ---------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _par_tables(e):
+        """(par_beg, par_len) of spe_grad_report for one bucket: the reducer's (parameter, offset) table on the device."""
+        offs, dev = e["b"]["offsets"], e["m"].device
+        return (host_to_device([off for _, off in offs], torch.int64, dev), host_to_device([p.numel() for p, _ in offs], torch.int64, dev))
+
+    def _report_rows(self, recs, model):
+        """Rows of the report from one host copy of the records per bucket, in reducer order."""
+        names = {} if model is None else {p: n for n, p in model.named_parameters()}
+        rows = []
+        for bi, (e, rec) in enumerate(zip(self._buckets, recs)):
+            f, r = rec.view(torch.float32).tolist(), rec.tolist()
+            for i, (p, _) in enumerate(e["b"]["offsets"]):
+                first = r[i][K.REPORT_FIRST_BAD]
+                shape = tuple(p.shape)
+                idx = None
+                if first >= 0:
+                    idx, rest = [], first
+                    for d in reversed(shape):
+                        idx.append(rest % d); rest //= d
+                    idx = tuple(reversed(idx))
+                gsq, wsq = f[i][K.REPORT_GRAD_SQ], f[i][K.REPORT_WEIGHT_SQ]
+                rows.append({"name": names.get(p, f"bucket{bi}.param{i}"), "shape": shape, "numel": p.numel(),
+                             "nan": r[i][K.REPORT_NAN], "inf": r[i][K.REPORT_INF], "first_bad": idx,
+                             "grad_sq": gsq, "grad_norm": math.sqrt(gsq) if gsq == gsq else gsq, "grad_absmax": f[i][K.REPORT_GRAD_ABSMAX],
+                             "weight_norm": math.sqrt(wsq) if wsq == wsq else wsq, "weight_absmax": f[i][K.REPORT_WEIGHT_ABSMAX]})
+        return rows
+
+    def skip_report(self, model=None, top=5):
+        """What the guard skipped: None while no report has been written (no skipped step yet), otherwise a dict
+            "attempt"         1-based index, among the step() calls, of the skipped step the records describe ("first": == first_skipped())
+            "params"          one row per parameter, in reducer order: name, shape, numel, nan, inf, first_bad (index tuple or None),
+                              grad_sq, grad_norm, grad_absmax (of grad_scale * g over its finite elements), weight_norm, weight_absmax
+            "culprits"        the rows with nan + inf > 0 or a non-finite grad_sq (a finite element whose square overflows fp32)
+            "largest"         the `top` rows by grad_absmax
+            "total_overflow"  True when no row is a culprit: only the sum over all parameters left fp32, and "largest" is the answer
+        Names come from model.named_parameters() when model is given, "bucket{b}.param{i}" otherwise.  One small device-to-host copy
+        per bucket: synchronises.  With accumulation the rows describe the accumulated sum; every rank holds the same report."""
+        if self.skip_report_mode is None:
+            raise RuntimeError("FlatAdamW.skip_report() needs skip_report='first' or 'last' (the optimizer was built without the report)")
+        recs = [e["report"].cpu() for e in self._buckets]
+        attempt = int(recs[0][0, K.REPORT_ATTEMPT])
+        if attempt == 0:
+            return None
+        rows = self._report_rows(recs, model)
+        culprits = [r for r in rows if r["nan"] + r["inf"] > 0 or not math.isfinite(r["grad_sq"])]
+        largest = sorted(rows, key=lambda r: -r["grad_absmax"])[:top]
+        return {"attempt": attempt, "params": rows, "culprits": culprits, "largest": largest, "total_overflow": not culprits}
+
+    @torch.no_grad()
+    def grad_stats(self, model=None, raw=False):
+        """The rows of skip_report()["params"] for what the buckets hold NOW - per-parameter gradient norms and maxima (of
+        reducer.grad_scale() * g), NaN / inf counts, weight norms - from one unconditional spe_grad_report per bucket.  Needs neither
+        skip_nonfinite nor skip_report; its buffers are allocated on the first call.  raw=True: the device tensors (int32
+        [parameters, GRAD_REPORT_WORDS] per bucket, overwritten by the next call) and no host read; otherwise one small copy per
+        bucket (synchronises).  Call it after the backward (reducer.finish()) and before zero_grad().  After a step() with
+        write_clipped_grads=True the buckets hold the CLIPPED gradient with grad_scale folded in (the table multiplies by grad_scale
+        all the same: the same figures only while it is 1); before the step, the raw sums.  Inside an
+        open accumulation cycle the buckets hold one micro-batch: RuntimeError, as step()."""
+        if getattr(self.reducer, "micro", 0) != 0:
+            raise RuntimeError(f"FlatAdamW.grad_stats() inside an accumulation cycle: micro-step {self.reducer.micro} of accum_steps = "
+                               f"{self.reducer.accum_steps} comes next - the buckets hold one micro-batch, not the step's gradient")
+        for e in self._buckets:
+            if e["par_tab"] is None:
+                e["par_tab"] = self._par_tables(e)
+            if e["stats"] is None:
+                e["stats"] = torch.zeros((len(e["b"]["offsets"]), K.GRAD_REPORT_WORDS), device=e["m"].device, dtype=torch.int32)
+            K.grad_report(e["b"]["flat"], e["b"]["flat_p"], e["par_tab"][0], e["par_tab"][1], self.reducer.grad_scale(), e["stats"])
+        if raw:
+            return [e["stats"] for e in self._buckets]
+        return self._report_rows([e["stats"].cpu() for e in self._buckets], model)
 
     def _guard_counts(self):
         if self._guard is None:
