@@ -46,7 +46,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_adamw_flat_ema / spe_swap_flat (the weight EMA kept inside the optimizer's update launch, and its exchange with the parameters)
  * spe_linear_small_plan (the launch choices of the spe_linear_small_* entries, host only)
  * spe_grad_report (per-parameter gradient and weight statistics on the flat buckets, gated on the guard block: what a skipped step skipped)
- * - 110 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
+ * spe_cls_ap / spe_cls_ap_workspace (the multi-label classification AP of the image-label logits on the device)
+ * - 112 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -703,6 +704,25 @@ int spe_coco_match(const float* det_boxes, const long* det_cats, const int* det_
 int spe_coco_accumulate(const unsigned* words, const int* rank, const float* det_scores, const int* seg_off, const int* npig,
                         const int* max_dets, const double* rec_thrs, int num_cats, int num_rec, int num_max_dets, double* precision,
                         double* recall, double* scores, spe_stream_t stream);
+
+/* ---- multi-label classification AP (reference cams_deit.py:493-574, AveragePrecisionMeter.average_precision, the evaluator
+ * engine.py and engine_loc.py import; csrc/cls_ap.hip).  Compiled without FMA contraction; asynchronous; no atomics at all.
+ * Storage is class-major: class c owns scores[c * ld .. c * ld + n) (fp32) and targets[c * ld .. c * ld + n) (int8: 1 a positive, 0,
+ * anything else - the caller reduces to -1 - a negative); nothing at or beyond column n of a row is read.  Per class the samples are
+ * ranked: higher score first; scores that compare equal in fp32 (+0.0 and -0.0 included) by ascending sample index; a NaN score before
+ * every number (where torch.sort(descending=True) puts it), NaNs among themselves by index.  A sample is counted unless difficult != 0
+ * and its target is 0.  Walking the counted samples in rank order, every positive adds (double)pos_count / (double)total_count (both
+ * counts include it) to an fp64 sum, in walk order, and ap[c] = sum / (double)npos[c]: with a tie-free column the number the
+ * reference's Python loop returns, bit for bit.  npos[c] = 0: ap[c] = NaN (the reference raises ZeroDivisionError).
+ * npos[c] / ncounted[c] (int32): the positives / the counted samples of the class.  n = 0: ap = NaN, both counts 0, workspace unused.
+ * Two launches: one thread per (class, sample) counts the samples ranked at or before it by streaming the row through LDS - O(n^2)
+ * comparisons per class - and stores a positive's term at slot pos_count - 1 of the class's workspace row; one workgroup per class adds
+ * its npos[c] slots sequentially.  workspace: caller-owned device memory, 8-B aligned, n * C doubles (spe_cls_ap_workspace reports the
+ * bytes; host function, bytes: host pointer); contents need no initialisation.  ap / npos / ncounted: [C], every element written.
+ * -2, nothing launched: n < 0 or n > 2^24, C < 1 or C > 65535, ld < n; -4: workspace NULL with n > 0. */
+int spe_cls_ap_workspace(int n, int C, size_t* bytes);
+int spe_cls_ap(const float* scores, const signed char* targets, int n, int C, long ld, int difficult, double* workspace, double* ap,
+               int* npos, int* ncounted, spe_stream_t stream);
 
 /* ---- input transforms on the device (reference datasets/transforms.py + util/misc.collate_fn; csrc/img_resample.hip).
  * Pillow's Image.resize(..., BILINEAR) restated bit for bit: per axis, source length inS (after the crop) and output length outS,

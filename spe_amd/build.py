@@ -30,7 +30,9 @@ EXTRA_FLAGS = {"attn_flash_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # detect.hip restates PostProcess's fp32 box arithmetic and the NMS overlap test as elementwise compositions: one rounding per operation
                "detect.hip": ["-ffp-contract=off"],
                # grad_report.hip restates a fixed fp32 order of products and sums: a squared gradient must overflow exactly where the guard's does
-               "grad_report.hip": ["-ffp-contract=off"]}
+               "grad_report.hip": ["-ffp-contract=off"],
+               # cls_ap.hip restates a Python loop's fp64 divisions and additions one by one, like the other evaluators
+               "cls_ap.hip": ["-ffp-contract=off"]}
 
 
 def flags_for(src):

@@ -10,7 +10,8 @@ other side: an update whose reduced GRADIENT is not finite is skipped on the dev
 loss with finite gradients is still applied and still stops at the ledger's check.
 
 The evaluation loops `evaluate_det_voc` (reference engine_loc.py:127-201) and `evaluate_refinements` (engine.py:617-724) follow: the
-detection head (spe_amd.infer.detect) between the forward and a detection meter (spe_amd.evalmetrics), DESIGN.md section 8k."""
+detection head (spe_amd.infer.detect) between the forward and a detection meter (spe_amd.evalmetrics), DESIGN.md section 8k;
+`evaluate_det_voc` also feeds a caller's ClassificationAPMeter with the image-level logits."""
 import copy
 import time
 
@@ -201,12 +202,15 @@ def _coco_cat_ids(base_ds):
 
 @torch.no_grad()
 def evaluate_det_voc(model, criterion, postprocessors, data_loader, base_ds, device, output_dir, cache_dir, with_flip=False, *kargs,
-                     **kwargs):
+                     cls_meter=None, cls_key="x_logits", **kwargs):
     """engine_loc.py:127-201 with the VOC meter in place of the result files: top 300, per-class NMS at 0.5, AP (VOC07 11-point unless
     use_07_metric=False is passed) and CorLoc, printed in the lines of datasets/voc_voc.py:_eval_discovery and _do_python_eval (without
     the closing banner about the MATLAB code).  base_ds: image id (t['idx']) -> {'boxes' [g,4] annotation frame, 'labels' [g],
     'difficult' [g]}.  The class names come from data_loader.dataset.classes when it has them ('__background__' skipped), the class
-    count from there or from num_classes= (20).  Writes no files; returns the meter's summary (the reference returns None)."""
+    count from there or from num_classes= (20).  Writes no files; returns the meter's summary (the reference returns None).
+    cls_meter: an evalmetrics.ClassificationAPMeter (the reference's AveragePrecisionMeter, cams_deit.py:493-574) that is fed the raw
+    image-level logits outputs[cls_key] - with_flip: of the merged output - against the stacked t['label'] of every batch; after the
+    detection lines its per-class AP and the mean are printed and returned as 'cls_ap' (fp64 [C]) and 'cls_map'.  None: nothing of it."""
     from . import infer
     from .evalmetrics import VOCDetectionMeter
     from .util.misc import NestedTensor
@@ -234,6 +238,8 @@ def evaluate_det_voc(model, criterion, postprocessors, data_loader, base_ds, dev
         sizes = torch.stack([t["image_size"].flip(0) for t in targets], dim=0)
         det = infer.detect(outputs, sizes, 300, 0.5)
         meter.update(det.padded(), [{**gt_of(i), "image_id": t["idx"].reshape(())} for i, t in zip(ids, targets)])
+        if cls_meter is not None:
+            cls_meter.add(outputs[cls_key], torch.stack([t["label"] for t in targets]))      # logits, not sigmoids: no saturation ties
     meter.merge()
     out = meter.summarize(use_07_metric=use_07_metric)
     for what, per_class, mean in (("CorLoc", out["corloc"].tolist(), out["mean_corloc"]), ("AP", out["ap"].tolist(), out["map"])):
@@ -248,6 +254,14 @@ def evaluate_det_voc(model, criterion, postprocessors, data_loader, base_ds, dev
             print("{:.3f}".format(v))
         print("{:.3f}".format(mean))
         print("~~~~~~~~")
+    if cls_meter is not None:
+        cls_meter.merge()
+        cls = cls_meter.summarize()
+        cls_names = names if len(names) == cls["ap"].numel() else [f"class{c + 1}" for c in range(cls["ap"].numel())]
+        for name, v in zip(cls_names, cls["ap"].tolist()):
+            print("AP (cls) for {} = {:.4f}".format(name, v))
+        print("Mean AP (cls) = {:.4f}".format(cls["map"]))
+        out["cls_ap"], out["cls_map"] = cls["ap"], cls["map"]
     return out
 
 

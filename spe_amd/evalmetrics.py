@@ -1,4 +1,5 @@
-"""Detection metrics of the SPE evaluation loops, kept on the device.
+"""Metrics of the SPE evaluation loops, kept on the device: the two detection meters and, at the end of the file, the multi-label
+classification AP of the image-level logits (`ClassificationAPMeter`: reference cams_deit.py:493-574; `spe_cls_ap`).
 
 PASCAL VOC: the last step of reference
 `engine_loc.evaluate_det_voc` (engine_loc.py:176-197), i.e. `evaluate_detections` -> `voc_eval` (datasets/voc_voc.py:366-437,
@@ -513,3 +514,154 @@ class COCODetectionMeter(_DetectionMeter):
             end = int(seg_off[-1])
             out["records"] = {k: v[:end].cpu().numpy() for k, v in col.items()}
         return out
+
+
+# ---- multi-label classification AP (reference cams_deit.py:493-574, AveragePrecisionMeter) --------------------
+def _cls_ap_host(scores, targets, n, difficult):
+    """kernels.cls_ap on CPU tensors: per class a stable sort by (-score, index) with NaN in front, integer running counts, the fp64
+    quotients and their sequential sum.  -> (ap fp64 [C], npos int32 [C], ncounted int32 [C]) as numpy arrays."""
+    sc, tg = scores.numpy()[:, :n], targets.numpy()[:, :n]
+    C = sc.shape[0]
+    ap, npos, ncounted = np.full(C, np.nan), np.zeros(C, np.int32), np.zeros(C, np.int32)
+    for c in range(C):
+        nan = np.isnan(sc[c])
+        order = np.lexsort((np.where(nan, 0.0, -sc[c].astype(np.float64)), ~nan))      # stable; last key first: NaN, then -score (-0.0 == 0.0)
+        t = tg[c][order]
+        t = t[t != 0] if difficult else t
+        positive = t == 1
+        npos[c], ncounted[c] = int(positive.sum()), t.size
+        if npos[c]:
+            terms = np.cumsum(positive)[positive].astype(np.float64) / (np.nonzero(positive)[0] + 1).astype(np.float64)
+            ap[c] = np.cumsum(terms)[-1] / float(npos[c])                              # cumsum: a fixed, sequential order
+    return ap, npos, ncounted
+
+
+class ClassificationAPMeter:
+    """Accumulates the per-class average precision of multi-label image classification over an evaluation run: the reference's
+    AveragePrecisionMeter (cams_deit.py:493-574), what says whether the class tokens ('x_logits', 'x_cls_logits') - and with them the
+    CAM branch behind every pseudo box - are healthy.
+
+        m = ClassificationAPMeter(difficult_examples=False)
+        m.add(outputs['x_logits'], torch.stack([t['label'] for t in targets]))     # per batch: [B, C] logits, [B, C] multi-hot labels
+        m.merge()                  # once, when the images were split over ranks
+        out = m.summarize()        # {'ap' fp64 [C], 'map', 'npos' int32 [C], 'ncounted' int32 [C]}
+        m.value()                  # the reference's return: ap as fp32 [C]
+
+    reset(), add(output, target) and value() keep the reference's names and shape rules: a 1-D input is one column, a 2-D one is
+    [B, C], a later add with another C raises.  Targets of any dtype are reduced to int8 on their device (== 1 -> 1, a positive;
+    == 0 -> 0; anything else -> -1, a negative like 0 - but with difficult_examples a 0 is skipped and a -1 is not); scores are kept
+    as fp32.  Pass raw logits: a sigmoid is monotone, but its fp32 saturation makes ties the logits do not have.  Storage is class-major
+    [C][capacity], on the device of the first add, and grows geometrically; add() does not read device data on the host.
+
+    Per class: higher score first; scores that compare equal in fp32 (+0.0 and -0.0 included) rank by ascending sample index - the
+    order of add(), after merge() rank-major; a NaN score ranks before every number, NaNs among themselves by index.  At every counted
+    positive, in that order, pos_count / total_count is added in fp64, and the sum is divided by the number of positives.  On
+    tie-free input this is the reference's number bit for bit (its torch.sort promises no tie order; this rule is the package's own).
+    A class without a counted positive has ap NaN (the reference raises ZeroDivisionError) and takes no part in 'map'; 'map' is NaN
+    when no class has one.  CUDA tensors take csrc/cls_ap.hip (one call, one copy per summarize(); it ranks by counting, N comparisons
+    per sample and class - 0.4 ms at N 5000, C 90, profiles/cls_ap_meter.txt - and is not meant for millions of samples); CPU tensors
+    take a numpy composition of the same rules."""
+    _MIN_CAPACITY = 1024
+
+    def __init__(self, difficult_examples=False):
+        self.difficult_examples = bool(difficult_examples)
+        self.reset()
+
+    def reset(self):
+        self._device, self._C, self._n = None, None, 0
+        self._scores = self._targets = None    # [C][capacity] fp32 / int8, the first _n columns valid
+        self._merged = False
+
+    @staticmethod
+    def _columns(x, what):
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.asarray(x))
+        if x.dim() == 1:
+            return x.reshape(-1, 1)
+        if x.dim() != 2:
+            raise ValueError(f"wrong {what} size (should be 1D or 2D with one column per class)")
+        return x
+
+    def _reserve(self, n, C, dev):
+        """Room for n samples: a new allocation and one copy when the capacity is exceeded (geometric growth)."""
+        if self._scores is not None and n <= self._scores.shape[1]:
+            return
+        cap, old = max(2 * n, self._MIN_CAPACITY), (self._scores, self._targets)
+        self._scores = torch.empty((C, cap), dtype=torch.float32, device=dev)
+        self._targets = torch.empty((C, cap), dtype=torch.int8, device=dev)
+        if old[0] is not None:
+            self._scores[:, :self._n] = old[0][:, :self._n]
+            self._targets[:, :self._n] = old[1][:, :self._n]
+
+    @torch.no_grad()
+    def add(self, output, target):
+        if self._merged:
+            raise RuntimeError("ClassificationAPMeter: add() after merge(); reset() first")
+        output, target = self._columns(output, "output"), self._columns(target, "target")
+        if output.shape != target.shape:
+            raise ValueError(f"ClassificationAPMeter.add: output {tuple(output.shape)} and target {tuple(target.shape)} differ")
+        B, C = output.shape
+        if self._C is not None and C != self._C:
+            raise ValueError("dimensions for output should match previously added examples.")
+        if self._device is None:
+            self._device = output.device
+        elif output.device != self._device:
+            raise ValueError(f"ClassificationAPMeter: tensors on {output.device}, earlier adds on {self._device}")
+        if self._n + B > K.CLS_AP_MAX_N:
+            raise ValueError(f"ClassificationAPMeter: at most {K.CLS_AP_MAX_N} samples")
+        self._C = C
+        self._reserve(self._n + B, C, self._device)
+        target = target.to(self._device)
+        code = (target == 1).to(torch.int8) - ((target != 1) & (target != 0)).to(torch.int8)      # 1 / 0 / -1 (a NaN target: -1)
+        self._scores[:, self._n:self._n + B] = output.detach().to(torch.float32).t()
+        self._targets[:, self._n:self._n + B] = code.t()
+        self._n += B
+
+    def merge(self, group=None):
+        """Concatenate the samples of every rank in rank order: afterwards every rank summarizes the whole run.  A no-op without an
+        initialised process group.  A rank that added nothing takes part (it learns C from the others)."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        if self._merged:
+            raise RuntimeError("ClassificationAPMeter: merge() called twice; reset() first")
+        if self._device is None:
+            self._device = torch.device("cuda" if dist.get_backend(group) == "nccl" else "cpu")
+        dev, world = self._device, dist.get_world_size(group)
+        width = torch.tensor([self._C or 0], dtype=torch.int64, device=dev)
+        dist.all_reduce(width, op=dist.ReduceOp.MAX, group=group)
+        C = int(width)
+        if self._C is not None and self._C != C:
+            raise ValueError("ClassificationAPMeter.merge: the ranks hold different numbers of classes")
+        self._merged = True
+        if C == 0:                                                              # no rank added anything
+            return
+        self._C = C
+        if self._scores is None:
+            self._reserve(0, C, dev)
+        rows = [_all_gather_rows(t[:, :self._n].t().contiguous(), world, group) for t in (self._scores, self._targets)]
+        self._n = rows[0].shape[0]
+        self._scores, self._targets = rows[0].t().contiguous(), rows[1].t().contiguous()
+
+    @torch.no_grad()
+    def summarize(self):
+        """-> {'ap': fp64 [C] (NaN for a class without a counted positive), 'map': float (the mean over the classes that have one; NaN
+        if none has), 'npos': int32 [C], 'ncounted': int32 [C]} - CPU tensors and a float."""
+        if self._C is None:
+            raise RuntimeError("ClassificationAPMeter.summarize: nothing accumulated")
+        C = self._C
+        if self._device.type == "cuda":
+            out = K.cls_ap(self._scores, self._targets, self._n, self.difficult_examples).cpu()       # one call, one copy
+            counts = out[1].view(torch.int32)
+            ap, npos, ncounted = out[0].numpy().copy(), counts[:C].numpy().copy(), counts[C:].numpy().copy()
+        else:
+            ap, npos, ncounted = _cls_ap_host(self._scores, self._targets, self._n, self.difficult_examples)
+        have = npos > 0
+        return {"ap": torch.from_numpy(ap), "map": float(np.mean(ap[have])) if have.any() else float("nan"),
+                "npos": torch.from_numpy(npos), "ncounted": torch.from_numpy(ncounted)}
+
+    def value(self):
+        """The reference's return: the AP per class as fp32 [C]; 0 for an empty meter."""
+        if self._C is None or self._n == 0:
+            return 0
+        return self.summarize()["ap"].to(torch.float32)

@@ -1961,6 +1961,32 @@ def coco_accumulate(words, rank, scores, seg_off, npig, max_dets, rec_thrs):
     return prec, rec, sco
 
 
+# ---- multi-label classification AP (csrc/cls_ap.hip) -----------------------------------------------
+CLS_AP_MAX_N = 1 << 24     # samples per class spe_cls_ap takes (-2 beyond)
+
+
+def cls_ap_workspace_bytes(n, C):
+    b = ctypes.c_size_t(0)
+    lib.call("spe_cls_ap_workspace", int(n), int(C), ctypes.byref(b))
+    return b.value
+
+
+def cls_ap(scores, targets, n, difficult):
+    """Class-major storage scores fp32 [C, ld] / targets int8 [C, ld] (1 positive, 0, -1), the first n columns of every row valid
+    -> one fp64 device tensor [2, C]: row 0 the AP per class (NaN without a positive), row 1 viewed as int32 [2 * C] the positives [C]
+    then the counted samples [C] - what a caller that wants them on the host copies in one piece."""
+    _check_typed("cls_ap", ((scores, torch.float32), (targets, torch.int8)))
+    if scores.dim() != 2 or scores.shape != targets.shape:
+        raise ValueError("cls_ap: scores and targets must be [C, ld] of one shape")
+    C, ld = scores.shape
+    ws = torch.empty((cls_ap_workspace_bytes(n, C) // 8,), device=scores.device, dtype=torch.float64)
+    out = torch.empty((2, C), device=scores.device, dtype=torch.float64)
+    counts = out[1].view(torch.int32)
+    _call("spe_cls_ap", _p(scores), _p(targets), int(n), C, ld, int(bool(difficult)), _p(ws), _p(out[0]), _p(counts[:C]), _p(counts[C:]),
+          _st())
+    return out
+
+
 # ---- step ledger: weighted total, loss meters and non-finite guard of a training step (csrc/step_ledger.hip) ----------------------
 LEDGER_MAX_K, LEDGER_MAX_E, LEDGER_D = 256, 8, 64      # loss values per step, host scalars per step, ring rows (= the largest window)
 
