@@ -47,7 +47,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_linear_small_plan (the launch choices of the spe_linear_small_* entries, host only)
  * spe_grad_report (per-parameter gradient and weight statistics on the flat buckets, gated on the guard block: what a skipped step skipped)
  * spe_cls_ap / spe_cls_ap_workspace (the multi-label classification AP of the image-label logits on the device)
- * - 112 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
+ * spe_cam_targets / spe_refine_pick (the training targets assembled on the device: CAM boxes -> target rows, the stage k+1 picks in one launch)
+ * - 114 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -614,7 +615,7 @@ int spe_detect(const float* logits, const float* boxes, const float* sizes, int 
 /* ---- CAM -> pseudo boxes (reference cams_deit.py:9-13 resize_cam, :61-96 get_multi_bboxes; engine.py:356-398).
  * spe_cam_prepare (device): M class maps cams[M][h][w] -> thresholded uint8 images out[M][rows][cols]: bilinear resize
  * (cv2.INTER_LINEAR convention), min-max normalisation, (x*255) truncated to uint8, THRESH_TOZERO at
- * int(cam_thr * max).  minmax: 2*M floats of workspace.  Synchronises the stream once (workspace initialisation).
+ * int(cam_thr * max).  minmax: 2*M floats of workspace, contents need no initialisation.  Asynchronous.
  * spe_cam_contour_boxes (HOST function, host pointers): borders of the non-zero pixels of one image (Suzuki-Abe border
  * following, 8-connected, outer and hole borders = cv2.findContours RETR_TREE), polygon areas (cv2.contourArea) and the
  * boxes [x, y, x+w, y+h] (cv2.boundingRect) of every border with area >= area_ratio * largest, largest first;
@@ -638,6 +639,31 @@ int spe_cam_contour_boxes(const void* img, int rows, int cols, float area_ratio,
 int spe_cam_boxes_device_workspace(int M, int rows, int cols, size_t* bytes);
 int spe_cam_boxes_device(const void* img, int M, int rows, int cols, float area_ratio, void* workspace, size_t workspace_bytes,
                          int* boxes, int* nboxes, int max_boxes, spe_stream_t stream);
+
+/* ---- training targets on the device (csrc/train_targets.hip): the step between the forward and the criterion of
+ * the refine training loops (reference engine.py:356-398 and models/conditional_detr.py:641-677), without a host loop over boxes.
+ * spe_cam_targets: packed = the result of spe_cam_boxes_device as it lies on the device, counts [M] then boxes [M][max_boxes][4] int32
+ *   [x, y, x+w, y+h]; cls0 [M] (int32, device): the 0-based class of every map, the maps image-major with classes ascending.  Rows
+ *   0 .. T-1 of boxes [cap][4] (fp32, 16-B aligned) and labels [cap] (int64) are the concatenation over the maps, in table order, of each
+ *   map's first counts[m] boxes - single != 0: of its first box - as normalised cxcywh, label cls0[m] + 1; off [M + 1] (int32) is the
+ *   first row of every map and off[M] = T.  A negative count is a status of spe_cam_boxes_device: it contributes no row and stays where
+ *   it is for the caller to raise on.  Rows T .. cap-1 are not written.  The arithmetic is the host's, one rounding per operation:
+ *   cx = float(x0 + x1) / 2.f / W, w = float(x1 - x0) / W, likewise y with H.  One workgroup: an exclusive scan over M in chunks with a
+ *   carry, then one thread per row; asynchronous, nothing is read back.
+ *   -2: M > 65535 or max_boxes > 2048 (the limits of spe_cam_boxes_device); -3: M < 0, max_boxes < 1, W or H < 1, a NULL or misaligned
+ *   buffer, cap < M * (single ? 1 : max_boxes) - the counts are not known on the host, so the worst case must fit.  M = 0 writes off[0] = 0.
+ * spe_refine_pick: prob [B][Q][Kc] (the sigmoid of the logits), pred_boxes [B][Q][4]; cls [U] (int32): per image its class ids, image b
+ *   owning rows cls_off[b] .. cls_off[b+1] (int32 [B + 1]); both tables on the device, and once more on the HOST (cls_host, cls_off_host;
+ *   NULL: unchecked) for the argument check.  For every row u of image b and class c: the best query of prob[b][.][c] by torch.max's rule
+ *   - the largest value wins, equal values: the lowest query, a NaN beats every number and the first NaN wins - scores[u] = that value bit
+ *   for bit, queries[u] (int32) = that query, boxes[u][4] = pred_boxes[b][query].  One wave per row, lanes stride over the queries, no
+ *   atomics: bitwise reproducible.  Any Q >= 1; U = 0 and images without a class are valid (nothing launched for U = 0).
+ *   -3: B < 0, Q < 1, Kc < 1, U < 0, a NULL buffer, host offsets that do not start at 0, descend or do not end at U, a host class id
+ *   outside [0, Kc).  A device class id outside [0, Kc) that the host did not see reads nothing and leaves its row unwritten. */
+int spe_cam_targets(const int* packed, const int* cls0, int M, int max_boxes, int single, int W, int H, int cap, float* boxes,
+                    long* labels, int* off, spe_stream_t stream);
+int spe_refine_pick(const float* prob, const float* pred_boxes, const int* cls, const int* cls_off, const int* cls_host,
+                    const int* cls_off_host, int B, int Q, int Kc, int U, float* scores, int* queries, float* boxes, spe_stream_t stream);
 
 /* ---- PASCAL VOC detection metrics (reference engine_loc.py:176-197, datasets/voc_eval.py, datasets/dis_eval.py; csrc/voc_eval.hip).
  * All arithmetic is fp64 in numpy's operation order, compiled without FMA contraction: with equal inputs the overlaps, and so every

@@ -37,6 +37,11 @@ __device__ __forceinline__ void atomic_minmax(float* mm, float lo, float hi) {
     if (l >= 0) atomicMin(mi, l); else atomicMax(reinterpret_cast<unsigned*>(mi), (unsigned)l);
     if (h >= 0) atomicMax(mi + 1, h); else atomicMin(reinterpret_cast<unsigned*>(mi + 1), (unsigned)h);
 }
+// min slot = +inf, max slot = -inf: set on the device, so that the entry point stays asynchronous
+__global__ __launch_bounds__(256) void cam_minmax_init_kernel(float* __restrict__ mm, int M) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m < M) { mm[2 * m] = INFINITY; mm[2 * m + 1] = -INFINITY; }
+}
 __global__ __launch_bounds__(256) void cam_minmax_kernel(const float* __restrict__ cams, float* __restrict__ mm, int h, int w,
                                                          int rows, int cols) {
     __shared__ float red[16];
@@ -74,13 +79,8 @@ __global__ __launch_bounds__(256) void cam_quantise_kernel(const float* __restri
 extern "C" int spe_cam_prepare(const float* cams, int M, int h, int w, int rows, int cols, float cam_thr, float* minmax,
                                unsigned char* out, hipStream_t st) {
     if (M <= 0 || rows <= 0 || cols <= 0) return 0;
-    // min slot = +inf, max slot = -inf
-    std::vector<float> init(2 * (size_t)M);
-    for (int i = 0; i < M; ++i) { init[2 * i] = INFINITY; init[2 * i + 1] = -INFINITY; }
-    hipError_t e = hipMemcpyAsync(minmax, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return (int)e;
-    e = hipStreamSynchronize(st);                           // `init` is pageable and goes out of scope
-    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(cam_minmax_init_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, minmax, M);
+    SPE_CHECK_LAUNCH();
     long nb = ((long)rows * cols + 255) / 256; if (nb > 1024) nb = 1024;
     hipLaunchKernelGGL(cam_minmax_kernel, dim3((unsigned)nb, M), dim3(256), 0, st, cams, minmax, h, w, rows, cols);
     SPE_CHECK_LAUNCH();

@@ -17,7 +17,7 @@ import time
 
 import torch
 
-from . import camboxes
+from . import camboxes, infer
 from .steplog import StepLedger
 
 PRINT_FREQ = 100
@@ -120,12 +120,19 @@ def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, devic
     if flat:
         optimizer.max_grad_norm = max_norm if max_norm > 0 else None     # the clip rides on the update launch
     for samples, targets in ledger.log_every(data_loader, PRINT_FREQ, header):
+        present = camboxes.present_lists(targets, "img_label")         # the loader's HOST tensors, before they move: a read, no synchronisation
         samples = samples.to(device)
         targets = [{k: v.to(device) for k, v in t.items()} for t in targets]
         outputs = model(samples)
-        pseudo_label = camboxes.get_pseudo_label_multi_boxes(outputs[0], samples, targets, args)
-        for t, p in zip(targets, pseudo_label):
+        # get_pseudo_label_multi_boxes with the target rows assembled on the device: the box counts are the one read between the forward
+        # and the criterion.  The class lists follow from the counts, so PostProcessRefine gets its
+        # `labels_unique` without torch.unique and picks the stage k+1 targets in one launch per stage.
+        pseudo = camboxes.pseudo_targets(outputs[0], samples, present, args.num_classes, args.cam_thr, args.multi_box_ratio)
+        logits = outputs[0]["pred_logits"]
+        uniq = infer.ClassTable([[c for c in cl if c < logits.shape[2]] for cl in pseudo.classes], logits.device).per_image()
+        for t, p, u in zip(targets, pseudo.per_image(), uniq):
             t.update(p)
+            t["labels_unique"] = u
         pseudo_label_refine = get_refinements_pseudo_label(outputs, samples, targets, args, postprocessors)
         loss_dict = criterion(outputs[0], targets)
         for rf, out in outputs.items():
@@ -211,7 +218,6 @@ def evaluate_det_voc(model, criterion, postprocessors, data_loader, base_ds, dev
     cls_meter: an evalmetrics.ClassificationAPMeter (the reference's AveragePrecisionMeter, cams_deit.py:493-574) that is fed the raw
     image-level logits outputs[cls_key] - with_flip: of the merged output - against the stacked t['label'] of every batch; after the
     detection lines its per-class AP and the mean are printed and returned as 'cls_ap' (fp64 [C]) and 'cls_map'.  None: nothing of it."""
-    from . import infer
     from .evalmetrics import VOCDetectionMeter
     from .util.misc import NestedTensor
     model.eval()
@@ -278,7 +284,6 @@ def evaluate_refinements(model, criterion, postprocessors, data_loader, base_ds,
     `_unscaled`, class_error with window 1), top 100, per-class NMS at 0.5, the COCO meter.  base_ds: image id (t['image_id']) ->
     {'boxes' [g,4] xywh, 'labels' [g], 'iscrowd' [g], 'area' [g]}; the category ids are base_ds.getCatIds() / base_ds.cat_ids, or every
     label of a mapping.  -> (stats, meter): the global averages of the ledger plus stats['coco_eval_bbox'], COCOeval's twelve numbers."""
-    from . import infer
     from .evalmetrics import COCODetectionMeter
     for k in ("segm", "panoptic"):
         if k in postprocessors:

@@ -170,3 +170,98 @@ def detect(outputs, target_sizes, keep_queries=100, iou_threshold=0.5, nms=True)
     if logits.is_cuda:
         return Detections(*K.detect(logits, boxes, sizes, keep_queries, iou_threshold, nms))
     return Detections(*_detect_host(logits, boxes, sizes, int(keep_queries), iou_threshold, nms))
+
+
+# ---- the stage k+1 training targets: PostProcessRefine's picks in one launch (csrc/train_targets.hip) ------------
+class ClassTable:
+    """The class ids PostProcessRefine picks for, per image sorted and below Kc, in the forms the pick needs: `lists` (host), `off`
+    (host offsets [B + 1]), and on the device `labels` int64 [U], `cls` int32 [U], `cls_off` int32 [B + 1] - ONE pinned upload, made
+    once per step and shared by the refinement stages.  `host` is None for a table gathered from device tensors (nobody has seen its
+    values on the host: the library cannot check them)."""
+
+    def __init__(self, lists, device):
+        self.lists = [[int(c) for c in l] for l in lists]
+        self.off = [0]
+        for l in self.lists:
+            self.off.append(self.off[-1] + len(l))
+        U, B = self.off[-1], len(self.lists)
+        flat = np.array([c for l in self.lists for c in l], np.int64)
+        self.host = (flat.astype(np.int32), np.array(self.off, np.int32))
+        self.device = torch.device(device)
+        if self.device.type == "cuda":
+            raw = K.host_table(np.concatenate([flat.view(np.uint8), self.host[0].view(np.uint8), self.host[1].view(np.uint8)]), device)
+            self._raw = raw
+            self.labels = raw[:8 * U].view(torch.int64)
+            self.cls, self.cls_off = raw[8 * U:12 * U].view(torch.int32), raw[12 * U:12 * U + 4 * (B + 1)].view(torch.int32)
+        else:
+            self.labels = torch.from_numpy(flat)
+            self.cls = self.cls_off = None
+
+    def per_image(self):
+        """One int64 view per image on the device: what a target dict carries as 'labels_unique'.  Every view knows its table."""
+        out = []
+        for b in range(len(self.lists)):
+            v = self.labels[self.off[b]:self.off[b + 1]]
+            v._spe_class_table = (self, b)
+            out.append(v)
+        return out
+
+    @classmethod
+    def of(cls, labs, device):
+        """The table behind a batch's 'labels_unique' tensors: the one they are views of, or a new one - from host tensors by value, from
+        device tensors gathered on the device (two launches, no host read, no host check)."""
+        tags = [getattr(l, "_spe_class_table", None) for l in labs]
+        if tags and all(t is not None and t[0] is tags[0][0] and t[1] == b for b, t in enumerate(tags)) \
+                and len(tags) == len(tags[0][0].lists) and tags[0][0].device == torch.device(device):
+            return tags[0][0]
+        if not any(l.is_cuda for l in labs):
+            return cls([l.reshape(-1).tolist() for l in labs], device)
+        self = cls.__new__(cls)
+        self.lists = self.host = None
+        self.off = [0]
+        for l in labs:
+            self.off.append(self.off[-1] + l.numel())
+        self.device = torch.device(device)
+        self.labels = torch.cat([l.reshape(-1).to(device=device, dtype=torch.int64) for l in labs]) if labs else torch.zeros((0,), dtype=torch.int64, device=device)
+        self.cls = self.labels.to(torch.int32)
+        key = (self.device, tuple(self.off))
+        if key not in _OFFSET_TABLES:                    # a loader's batches repeat a few size patterns: one upload each
+            if len(_OFFSET_TABLES) >= 256:
+                _OFFSET_TABLES.clear()
+            _OFFSET_TABLES[key] = K.host_table(np.array(self.off, np.int32).view(np.uint8), device).view(torch.int32)
+        self.cls_off = _OFFSET_TABLES[key]
+        return self
+
+
+_OFFSET_TABLES = {}         # (device, offsets) -> the offsets on the device, for the tables gathered from device tensors
+
+
+def _refine_pick_host(prob, boxes, table):
+    """kernels.refine_pick on CPU tensors: torch.max's own pick per image and the three gathers of PostProcessRefine."""
+    top_values, top_indexes = torch.max(prob, dim=1)
+    B, Kc = top_values.shape
+    lab = table.labels
+    if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= Kc):
+        raise ValueError(f"refine_targets: class ids must lie in [0, {Kc})")
+    img = torch.repeat_interleave(torch.arange(B), torch.tensor([table.off[b + 1] - table.off[b] for b in range(B)], dtype=torch.long))
+    q = top_indexes[img, lab]
+    return top_values[img, lab], q.to(torch.int32), boxes[img, q]
+
+
+@torch.no_grad()
+def refine_targets(outputs, classes):
+    """outputs: {'pred_logits' [B, Q, Kc], 'pred_boxes' [B, Q, 4]}; classes: per image the sorted class ids below Kc (host lists) or a
+    ClassTable -> {'scores' [U], 'labels' [U] int64, 'boxes' [U, 4] normalised cxcywh, 'queries' [U] int32, 'offsets' host list [B + 1]}:
+    PostProcessRefine's per-image results, flat - for every class of an image the best query by torch.max's rule over the probabilities
+    (the sigmoid ATen computes, one launch: bitwise PostProcessRefine's scores), equal probabilities to the lowest query, the first NaN
+    before everything.  On the device: the sigmoid and ONE HIP launch, no host read; CPU tensors take torch.max and the gathers."""
+    logits, boxes = outputs["pred_logits"], outputs["pred_boxes"]
+    table = classes if isinstance(classes, ClassTable) else ClassTable(classes, logits.device)
+    if len(table.off) != logits.shape[0] + 1:
+        raise ValueError(f"refine_targets: {len(table.off) - 1} class lists for {logits.shape[0]} images")
+    prob = logits.sigmoid()
+    if logits.is_cuda:
+        scores, queries, picked = K.refine_pick(prob.float().contiguous(), boxes.float().contiguous(), table.cls, table.cls_off, host=table.host)
+    else:
+        scores, queries, picked = _refine_pick_host(prob, boxes, table)
+    return {"scores": scores, "labels": table.labels, "boxes": picked, "queries": queries, "offsets": table.off}

@@ -1821,6 +1821,68 @@ def cam_boxes_device(imgs_u8_device, area_ratio, max_boxes=256):
     return out[M:].view(M, max_boxes, 4), out[:M]
 
 
+# ---- training targets (csrc/train_targets.hip) -------------------------------------------------------------
+CAM_TARGETS_MAX_M = 65535  # maps per launch spe_cam_targets takes (-2 beyond)
+
+
+def cam_targets(packed, cls0, max_boxes, single, W, H, cap=None, out=None):
+    """The packed int32 result of cam_boxes_device_packed ([M] counts, then [M, max_boxes, 4] boxes) and the 0-based class of every map
+    (int32 [M], device) -> (boxes fp32 [cap, 4] normalised cxcywh, labels int64 [cap] = class + 1, off int32 [M + 1]): rows 0 .. off[M]-1
+    are the maps' boxes in table order (single: the first box of every map), the rows behind are not written.  cap: at least the worst
+    case M * (1 if single else max_boxes), which is the default.  out: the three buffers to write into.  Nothing is read back."""
+    if not (packed.is_cuda and cls0.is_cuda):
+        raise lib.SpeLibraryError("spe_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    M = cls0.numel()
+    if packed.dtype != torch.int32 or cls0.dtype != torch.int32 or not (packed.is_contiguous() and cls0.is_contiguous()):
+        raise TypeError("cam_targets: contiguous int32 tables only")
+    if packed.numel() != M * (1 + 4 * max_boxes):
+        raise ValueError(f"cam_targets: {packed.numel()} packed words do not hold {M} maps of {max_boxes} boxes")
+    if cap is None:
+        cap = M * (1 if single else max_boxes)
+    if out is None:
+        out = (torch.empty((cap, 4), device=packed.device, dtype=torch.float32), torch.empty((cap,), device=packed.device, dtype=torch.int64),
+               torch.empty((M + 1,), device=packed.device, dtype=torch.int32))
+    boxes, labels, off = out
+    _check_typed("cam_targets", ((boxes, torch.float32), (labels, torch.int64), (off, torch.int32)))
+    if boxes.numel() < 4 * cap or labels.numel() < cap or off.numel() < M + 1:
+        raise ValueError("cam_targets: `out` is smaller than cap rows / M + 1 offsets")
+    _call("spe_cam_targets", _p(packed), _p(cls0), M, int(max_boxes), 1 if single else 0, int(W), int(H), int(cap), _p(boxes), _p(labels),
+          _p(off), _st())
+    return boxes, labels, off
+
+
+def refine_pick(prob, pred_boxes, cls, cls_off, host=None, out=None):
+    """prob [B, Q, Kc] (sigmoid of the logits), pred_boxes [B, Q, 4]; cls int32 [U] and cls_off int32 [B + 1] on the device: the class ids
+    of every image -> (scores [U], queries int32 [U], boxes [U, 4]): per (image, class) the best query by torch.max's rule (largest value,
+    equal values the lowest query, the first NaN beats everything), its probability bit for bit and its box.  host: the two tables as int32
+    numpy arrays, checked by the library before the launch (a class id outside [0, Kc) is status -3).  One launch, nothing is read back."""
+    _chk(prob, pred_boxes)
+    B, Q, Kc = prob.shape
+    U = cls.numel()
+    if pred_boxes.shape != (B, Q, 4) or cls_off.numel() != B + 1:
+        raise ValueError(f"refine_pick: boxes {tuple(pred_boxes.shape)} / {cls_off.numel()} offsets do not fit prob {tuple(prob.shape)}")
+    _check_typed("refine_pick", ((cls, torch.int32), (cls_off, torch.int32)))
+    if not (prob.is_contiguous() and pred_boxes.is_contiguous()):
+        raise ValueError("refine_pick: contiguous tensors only")
+    dev = prob.device
+    if out is None:
+        out = (torch.empty((U,), device=dev, dtype=torch.float32), torch.empty((U,), device=dev, dtype=torch.int32),
+               torch.empty((U, 4), device=dev, dtype=torch.float32))
+    scores, queries, boxes = out
+    _check_typed("refine_pick", ((scores, torch.float32), (queries, torch.int32), (boxes, torch.float32)))
+    if scores.numel() < U or queries.numel() < U or boxes.numel() < 4 * U:
+        raise ValueError("refine_pick: `out` is smaller than U rows")
+    hc = ho = None
+    if host is not None:
+        import numpy as np
+        hc, ho =(np.ascontiguousarray(h, dtype=np.int32) for h in host)
+        if hc.size != U or ho.size != B + 1:
+            raise ValueError("refine_pick: the host tables do not have the device tables' sizes")
+    _call("spe_refine_pick", _p(prob), _p(pred_boxes), _p(cls), _p(cls_off), None if hc is None else hc.ctypes.data,
+          None if ho is None else ho.ctypes.data, B, Q, Kc, U, _p(scores), _p(queries), _p(boxes), _st())
+    return scores, queries, boxes
+
+
 def pos_sine(mask_bool, dim_t, npf, scale, eps, normalize):
     """mask [B,h,w] bool (True = padded) -> [B,h,w,2*npf] fp32 sine position features (csrc/misc.hip)."""
     B, h, w = mask_bool.shape

@@ -323,6 +323,9 @@ class PostProcess(nn.Module):
         return [{"scores": s, "labels": l, "boxes": b} for s, l, b in zip(topk_values, labels, boxes)]
 
 
+REFINE_KERNEL = True        # tests: False keeps PostProcessRefine on the ATen composition, the yardstick of the one-launch pick
+
+
 class PostProcessRefine(nn.Module):
     """Stage-k detections -> stage-(k+1) pseudo targets (conditional_detr.py:641-677): for every class
     present in an image's labels (ascending id) the best query's score and NORMALISED cxcywh box."""
@@ -331,6 +334,14 @@ class PostProcessRefine(nn.Module):
     def forward(self, outputs, target_sizes, targets=None):
         out_logits, out_bbox = outputs["pred_logits"], outputs["pred_boxes"]
         assert len(out_logits) == len(target_sizes) and target_sizes.shape[1] == 2
+        if REFINE_KERNEL and out_logits.is_cuda and out_logits.dtype == torch.float32 and all("labels_unique" in t for t in targets):
+            # every class list is known without reading the labels: the sigmoid and ONE launch for the whole batch (csrc/train_targets.hip;
+            # spe_amd.infer.refine_targets), the same picks as the composition below, which stays for everything else
+            from .. import infer
+            r = infer.refine_targets(outputs, infer.ClassTable.of([t["labels_unique"] for t in targets], out_logits.device))
+            o = r["offsets"]
+            return [{"scores": r["scores"][o[b]:o[b + 1]], "labels": r["labels"][o[b]:o[b + 1]], "boxes": r["boxes"][o[b]:o[b + 1]]}
+                    for b in range(len(targets))]
         prob = out_logits.sigmoid()
         top_values, top_indexes = torch.max(prob, dim=1)                        # [B,Kc]
         res = []
