@@ -48,7 +48,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_grad_report (per-parameter gradient and weight statistics on the flat buckets, gated on the guard block: what a skipped step skipped)
  * spe_cls_ap / spe_cls_ap_workspace (the multi-label classification AP of the image-label logits on the device)
  * spe_cam_targets / spe_refine_pick (the training targets assembled on the device: CAM boxes -> target rows, the stage k+1 picks in one launch)
- * - 114 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
+ * spe_pseudo_quality (the quality of the pseudo labels against the loader's ground truth: per-class counters kept on the device)
+ * - 115 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -664,6 +665,30 @@ int spe_cam_targets(const int* packed, const int* cls0, int M, int max_boxes, in
                     long* labels, int* off, spe_stream_t stream);
 int spe_refine_pick(const float* prob, const float* pred_boxes, const int* cls, const int* cls_off, const int* cls_host,
                     const int* cls_off_host, int B, int Q, int Kc, int U, float* scores, int* queries, float* boxes, spe_stream_t stream);
+
+/* ---- pseudo-label quality on the device (csrc/pseudo_quality.hip): CorLoc, precision, recall and mean IoU of the rows
+ * the refine training loops feed their criteria, against the loader's ground-truth rows.  The reference reaches this view only through its
+ * evaluator (engine_loc.py:204-220, pseudo_label_to_det_out); here it is ten int64 counters per class that stay on the device.
+ * spe_pseudo_quality: pseudo rows of the batch concatenated, image b owning rows off[b] .. off[b+1] (int32 [B + 1], device): boxes [T][4]
+ *   normalised cxcywh, labels [T] (int64), scores [T] or NULL; ground truth likewise with goff: gboxes [G][4], glabels [G].  Both offset
+ *   vectors once more on the HOST (off_host, goff_host: required, the limits are checked on them before anything is launched).
+ *   counters: int64 [10][C + 1], ACCUMULATED in place.  The IoU is box_iou on box_cxcywh_to_xyxy of both rows in fp32, one rounding per
+ *   operation: corners cx -+ 0.5 * w, areas, max / min (a NaN on either side is the result), clamp(min=0), inter, (area1 + area2) - inter,
+ *   the division.  Rules: a label outside [0, C) on either side is counted in column C of counters 4 / 7 and takes no further part.  Best
+ *   IoU of a pseudo row: the maximum over the non-NaN IoUs with the same-label ground-truth rows of its image; without such a row it is an
+ *   orphan.  Hit: best IoU > iou_thresh (strict).  A ground-truth row is covered when a same-label pseudo row of its image has
+ *   IoU > iou_thresh with it.  Pair: an (image, class) with a ground-truth row.  Lead row of a pair: without scores the lowest pseudo row
+ *   of the class, with scores the largest score by spe_refine_pick's rule (equal scores: the lowest row; the first NaN before everything).
+ *   Counters per class: 0 pairs, 1 pairs whose lead row hits, 2 pairs with any hit, 3 pairs without a pseudo row, 4 pseudo rows, 5 rows
+ *   that hit, 6 orphan rows, 7 ground-truth rows, 8 covered ground-truth rows, 9 the sum over the non-orphan rows of
+ *   llrint(min(best, 1) * 2^20) for a finite positive best, else 0.
+ *   One workgroup of 256 threads per image, the ground truth and both label vectors in LDS; integer atomics only: bitwise reproducible.
+ *   Asynchronous, nothing is read back.  B = 0, or T = 0 and G = 0: status 0, nothing launched.
+ *   -2: more than 1024 pseudo rows or 1024 ground-truth rows in one image.  -3: B, T or G < 0, C < 1, host offsets that are NULL, do not
+ *   start at 0, descend or do not end at T / G, counters NULL, a NULL device buffer that has rows to hold. */
+int spe_pseudo_quality(const float* boxes, const long* labels, const float* scores, const int* off, const float* gboxes,
+                       const long* glabels, const int* goff, const int* off_host, const int* goff_host, int B, int T, int G, int C,
+                       float iou_thresh, long* counters, spe_stream_t stream);
 
 /* ---- PASCAL VOC detection metrics (reference engine_loc.py:176-197, datasets/voc_eval.py, datasets/dis_eval.py; csrc/voc_eval.hip).
  * All arithmetic is fp64 in numpy's operation order, compiled without FMA contraction: with equal inputs the overlaps, and so every

@@ -34,7 +34,9 @@ EXTRA_FLAGS = {"attn_flash_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # cls_ap.hip restates a Python loop's fp64 divisions and additions one by one, like the other evaluators
                "cls_ap.hip": ["-ffp-contract=off"],
                # train_targets.hip restates the host's fp32 box normalisation: an add, a halving and a division, each rounded on its own
-               "train_targets.hip": ["-ffp-contract=off"]}
+               "train_targets.hip": ["-ffp-contract=off"],
+               # pseudo_quality.hip restates box_iou's fp32 composition: products, sums and the division each rounded on their own, so iou > threshold decides alike
+               "pseudo_quality.hip": ["-ffp-contract=off"]}
 
 
 def flags_for(src):

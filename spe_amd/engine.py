@@ -103,8 +103,17 @@ def apply_curriculum_coco(weight_dict, epoch):
     return weight_dict
 
 
-def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, device, epoch, max_norm, args, postprocessors, criterion_refine):
+def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, device, epoch, max_norm, args, postprocessors, criterion_refine,
+                     pseudo_meter=None):
     """The loop of both public entries; `curriculum(weight_dict, epoch)` is what differs between them.
+
+    pseudo_meter: an evalmetrics.PseudoLabelMeter with the stages 'cam', 'rf_1' .. 'rf_<num_refines>' (DESIGN.md section 8o).  Every
+    batch scores the stage-0 targets and the targets of every refine stage against the loader's own 'boxes' / 'labels' (kept before the
+    pseudo labels replace them; a target without them raises ValueError): one launch per (step, stage), no host read.  After the loop the
+    meter is merged between the ranks and printed, and its four means per stage join the returned statistics as
+    pseudo_<stage>_corloc / _precision / _recall / _mean_iou.  The rows are scored in the frame the criterion receives them: CAM rows
+    normalised by the padded canvas (with the (H, W) -> dsize transposition of camboxes._pseudo_labels), ground truth by the image's own
+    size - on fixed square inputs the same frame, elsewhere the mismatch the criterion trains on.  None: nothing of it.
 
     Gradient accumulation: with a FlatAdamW whose reducer has accum_steps > 1 every iteration still does zero_grad / backward /
     finish() and is recorded in the ledger, optimizer.step() runs when finish() completed a cycle, and the micro-batches of a cycle
@@ -130,10 +139,19 @@ def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, devic
         pseudo = camboxes.pseudo_targets(outputs[0], samples, present, args.num_classes, args.cam_thr, args.multi_box_ratio)
         logits = outputs[0]["pred_logits"]
         uniq = infer.ClassTable([[c for c in cl if c < logits.shape[2]] for cl in pseudo.classes], logits.device).per_image()
+        if pseudo_meter is not None:
+            for key in ("boxes", "labels"):
+                if any(key not in t for t in targets):
+                    raise ValueError(f"pseudo_meter: the loader's targets carry no {key!r} to score the pseudo labels against")
+            gt = [{"boxes": t["boxes"], "labels": t["labels"]} for t in targets]
         for t, p, u in zip(targets, pseudo.per_image(), uniq):
             t.update(p)
             t["labels_unique"] = u
         pseudo_label_refine = get_refinements_pseudo_label(outputs, samples, targets, args, postprocessors)
+        if pseudo_meter is not None:
+            pseudo_meter.update("cam", pseudo, gt)
+            for rf, rows in pseudo_label_refine.items():
+                pseudo_meter.update(f"rf_{rf}", rows, gt)
         loss_dict = criterion(outputs[0], targets)
         for rf, out in outputs.items():
             if rf == 0:
@@ -165,21 +183,28 @@ def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, devic
                 print(format_skip_report(report))
     stats = ledger.global_avg()                 # synchronised between the ranks; raises if a step's total was not finite
     print("Averaged stats:", ledger)
+    if pseudo_meter is not None:
+        pseudo_meter.merge()
+        print(pseudo_meter)
+        for stage, r in pseudo_meter.summarize().items():
+            for k in ("corloc", "precision", "recall"):
+                stats[f"pseudo_{stage}_{k}"] = r["mean_" + k]
+            stats[f"pseudo_{stage}_mean_iou"] = r["mean_mean_iou"]
     return stats
 
 
 def train_one_epoch_refine(model, criterion, data_loader, optimizer, device, epoch, max_norm=0, args=None, postprocessors=None,
-                           criterion_refine=None):
-    """engine.py:93-174 (the VOC loop)."""
+                           criterion_refine=None, pseudo_meter=None):
+    """engine.py:93-174 (the VOC loop).  pseudo_meter: see _train_one_epoch."""
     return _train_one_epoch(apply_curriculum, model, criterion, data_loader, optimizer, device, epoch, max_norm, args, postprocessors,
-                            criterion_refine)
+                            criterion_refine, pseudo_meter=pseudo_meter)
 
 
 def train_one_epoch_refine_coco(model, criterion, data_loader, optimizer, device, epoch, max_norm=0, args=None, postprocessors=None,
-                                criterion_refine=None):
-    """engine.py:534-613 (the loop main_coco.py:356 calls): the same body with the COCO curriculum."""
+                                criterion_refine=None, pseudo_meter=None):
+    """engine.py:534-613 (the loop main_coco.py:356 calls): the same body with the COCO curriculum.  pseudo_meter: see _train_one_epoch."""
     return _train_one_epoch(apply_curriculum_coco, model, criterion, data_loader, optimizer, device, epoch, max_norm, args, postprocessors,
-                            criterion_refine)
+                            criterion_refine, pseudo_meter=pseudo_meter)
 
 
 # ---- evaluation loops (reference engine_loc.py:127-201, engine.py:617-724; DESIGN.md section 8k) -----------------------------------

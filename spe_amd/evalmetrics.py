@@ -1,5 +1,6 @@
 """Metrics of the SPE evaluation loops, kept on the device: the two detection meters and, at the end of the file, the multi-label
-classification AP of the image-level logits (`ClassificationAPMeter`: reference cams_deit.py:493-574; `spe_cls_ap`).
+classification AP of the image-level logits (`ClassificationAPMeter`: reference cams_deit.py:493-574; `spe_cls_ap`)
+and the one meter of the TRAINING loops, the quality of their pseudo labels (`PseudoLabelMeter`; `spe_pseudo_quality`; section 8o).
 
 PASCAL VOC: the last step of reference
 `engine_loc.evaluate_det_voc` (engine_loc.py:176-197), i.e. `evaluate_detections` -> `voc_eval` (datasets/voc_voc.py:366-437,
@@ -665,3 +666,211 @@ class ClassificationAPMeter:
         if self._C is None or self._n == 0:
             return 0
         return self.summarize()["ap"].to(torch.float32)
+
+
+# ---- pseudo-label quality (csrc/pseudo_quality.hip) ---------------------------------------------------------------
+def _pseudo_quality_host(boxes, labels, scores, off, gboxes, glabels, goff, C, iou_thresh, counters):
+    """kernels.pseudo_quality on CPU tensors, composed of torch operations per image: box_iou on the corners of both sides (fp32,
+    elementwise: one rounding per operation), masks for the same-label pairs, integer counts added into `counters` [10, C + 1]."""
+    from .util import box_ops
+    thr = torch.tensor(iou_thresh, dtype=torch.float32)
+    limit = K.PSEUDO_QUALITY_MAX_ROWS
+    B = len(off) - 1
+    if any(off[b + 1] - off[b] > limit or goff[b + 1] - goff[b] > limit for b in range(B)):
+        raise ValueError(f"PseudoLabelMeter: at most {limit} pseudo rows and {limit} ground-truth rows per image")
+
+    def classes(l):
+        return torch.where((l < 0) | (l >= C), torch.full_like(l, -1), l)
+
+    def add(k, cls, values=None):
+        counters[k].index_add_(0, cls, torch.ones_like(cls) if values is None else values)
+
+    for b in range(B):
+        p, g = slice(off[b], off[b + 1]), slice(goff[b], goff[b + 1])
+        pc, gc = classes(labels[p]), classes(glabels[g])
+        add(4, torch.where(pc < 0, torch.full_like(pc, C), pc))
+        add(7, torch.where(gc < 0, torch.full_like(gc, C), gc))
+        iou = box_ops.box_iou(box_ops.box_cxcywh_to_xyxy(boxes[p]), box_ops.box_cxcywh_to_xyxy(gboxes[g]))[0]          # [t, g]
+        same = (pc[:, None] == gc[None, :]) & (pc[:, None] >= 0)
+        best = torch.where(same & ~torch.isnan(iou), iou, torch.full_like(iou, float("-inf")))
+        best = best.max(dim=1).values if iou.shape[1] else torch.full((iou.shape[0],), float("-inf"))
+        matched = same.any(dim=1)
+        hit = matched & (best > thr)
+        add(5, pc[hit])
+        add(6, pc[(pc >= 0) & ~matched])
+        counted = matched & (best > 0) & torch.isfinite(best)
+        q = torch.round(best[counted].clamp(max=1) * float(K.PSEUDO_QUALITY_IOU_SCALE)).to(torch.int64)      # half to even, like llrint
+        add(9, pc[counted], q)
+        add(8, gc[(same & (iou > thr)).any(dim=0)])
+        sc = None if scores is None else scores[p]
+        for c in torch.unique(gc[gc >= 0]).tolist():
+            rows = torch.nonzero(pc == c).reshape(-1)
+            one = torch.tensor([c])
+            add(0, one)
+            if rows.numel() == 0:
+                add(3, one)
+                continue
+            lead = rows[0]
+            if sc is not None:
+                s = sc[rows]
+                nan = torch.isnan(s)
+                # the first NaN, else the first of the largest: argmax of a boolean takes the lowest index
+                lead = rows[(nan if bool(nan.any()) else s == s.max()).to(torch.uint8).argmax()]
+            if bool(hit[lead]):
+                add(1, one)
+            if bool(hit[rows].any()):
+                add(2, one)
+    return counters
+
+
+class PseudoLabelMeter:
+    """How good the boxes are that the refine training loops train on - the CAM boxes of stage 0, PostProcessRefine's picks of the later
+    stages - against the loader's ground truth, counted while training runs: CorLoc, precision, recall and mean IoU per class and stage.
+
+        m = PseudoLabelMeter(num_classes=21, stages=["cam", "rf_1", "rf_2"], iou_thresh=0.5)
+        m.update("cam", pseudo, gts)      # per batch and stage: one launch on the device, nothing read on the host
+        m.merge()                          # once, when the images were split over ranks: an all-reduce of the counters
+        out = m.summarize()                # {stage: {'corloc' fp64 [C], 'any_hit', 'precision', 'recall', 'mean_iou', 'mean_corloc', ...}}
+        print(m)                           # one line per stage
+
+    pseudo: a camboxes.PseudoTargets, the flat dict of infer.refine_targets ('boxes', 'labels', 'scores', 'offsets'), or the per-image list
+    of {'boxes', 'labels'[, 'scores']} that engine.get_refinements_pseudo_label returns.  gts: per image {'boxes' [g, 4], 'labels' [g]} in
+    normalised cxcywh, the loader's target rows.  num_classes = C: labels lie in [0, C) - with the loaders' 1-based labels, pass the
+    detector's class count (one more than the dataset's).
+
+    Rules (the package's own; csrc/pseudo_quality.hip).  IoU: box_iou on box_cxcywh_to_xyxy of both rows in fp32, the arithmetic the
+    criterion applies to these rows.  A label outside [0, C) on either side is counted ('dropped_rows', 'dropped_gts') and takes no
+    further part.  Best IoU of a pseudo row: the maximum over its non-NaN IoUs with the same-label ground-truth rows of its image;
+    without such a row it is an orphan.  Hit: best IoU > iou_thresh, strict (voc_eval.py, dis_eval.py:146).  A ground-truth row is
+    covered when a same-label pseudo row of its image has IoU > iou_thresh with it.  Pair: an (image, class) with a ground-truth row.
+    Lead row of a pair: without scores the lowest pseudo row of the class (CAM boxes: the largest border; PostProcessRefine: the only
+    one), with scores the largest score - equal scores to the lowest row, the first NaN before everything (spe_refine_pick's rule).
+    Per class: corloc = pairs whose lead row hits / pairs, any_hit = pairs with a hit / pairs, precision = rows that hit / rows,
+    recall = covered ground-truth rows / ground-truth rows, mean_iou = the mean best IoU of the non-orphan rows, each best IoU capped
+    at 1 and rounded to a multiple of 2^-20 (not finite or not positive: 0) - integer sums, so every number is a function of the input
+    alone.  A class with a zero denominator is NaN and takes no part in that stage's mean_* value (ClassificationAPMeter's rule).
+
+    The rows are scored in the frame the criterion receives them: CAM rows are normalised by the padded canvas of the batch - with the
+    (H, W) -> dsize transposition camboxes._pseudo_labels documents - and ground-truth rows by the image's own size.  On fixed square
+    inputs the frames coincide; elsewhere the meter reports the mismatch the criterion trains on, and does not rescale.
+
+    The state is int64 [stages, 10, C + 1] on the device of the first update.  CUDA tensors take spe_pseudo_quality (one launch per
+    update, both offset vectors in one pinned upload); CPU tensors take a torch composition of the same rules."""
+
+    def __init__(self, num_classes, stages, iou_thresh=0.5):
+        self.num_classes, self.stages, self.iou_thresh = int(num_classes), [str(s) for s in stages], float(iou_thresh)
+        if self.num_classes < 1:
+            raise ValueError("PseudoLabelMeter: num_classes must be at least 1")
+        if len(set(self.stages)) != len(self.stages) or not self.stages:
+            raise ValueError("PseudoLabelMeter: stages must be distinct names, at least one")
+        self.reset()
+
+    def reset(self):
+        self._counters = None              # int64 [S, 10, C + 1] on the device of the first update
+
+    def _state(self, device):
+        if self._counters is None:
+            self._counters = torch.zeros((len(self.stages), len(K.PSEUDO_QUALITY_COUNTERS), self.num_classes + 1), dtype=torch.int64,
+                                         device=device)
+        elif self._counters.device != device:
+            raise ValueError(f"PseudoLabelMeter: tensors on {device}, earlier updates on {self._counters.device}")
+        return self._counters
+
+    @staticmethod
+    def _cat(parts, dtype, tail, device):
+        parts = [p.detach().reshape((-1,) + tail).to(dtype) for p in parts]
+        if not parts:
+            return torch.zeros((0,) + tail, dtype=dtype, device=device)
+        return (torch.cat(parts) if len(parts) > 1 else parts[0]).contiguous()
+
+    def _flat(self, rows, device, what):
+        """-> boxes [n, 4] fp32, labels [n] int64, scores [n] fp32 or None, host offsets - out of any of the accepted forms."""
+        if hasattr(rows, "offsets") and hasattr(rows, "boxes"):                                 # camboxes.PseudoTargets
+            rows = {"boxes": rows.boxes, "labels": rows.labels, "offsets": rows.offsets}
+        if isinstance(rows, dict):
+            for k in ("boxes", "labels", "offsets"):
+                if k not in rows:
+                    raise ValueError(f"PseudoLabelMeter.update: the flat {what} rows have no {k!r}")
+            off = [int(o) for o in rows["offsets"]]
+            per = [rows]
+        else:
+            per, off = list(rows), [0]
+            for i, r in enumerate(per):
+                for k in ("boxes", "labels"):
+                    if k not in r:
+                        raise ValueError(f"PseudoLabelMeter.update: {what} rows of image {i} have no {k!r}")
+                off.append(off[-1] + r["labels"].shape[0])
+        if device is None:
+            device = per[0]["boxes"].device if per else torch.device("cpu")
+        boxes = self._cat([r["boxes"] for r in per], torch.float32, (4,), device)
+        labels = self._cat([r["labels"] for r in per], torch.int64, (), device)
+        scores = self._cat([r["scores"] for r in per], torch.float32, (), device) if per and all("scores" in r for r in per) else None
+        if boxes.shape[0] != off[-1] or labels.shape[0] != off[-1] or (scores is not None and scores.shape[0] != off[-1]):
+            raise ValueError(f"PseudoLabelMeter.update: {what} offsets end at {off[-1]}, the rows do not")
+        return boxes, labels, scores, off, device
+
+    @torch.no_grad()
+    def update(self, stage, pseudo, gts):
+        if stage not in self.stages:
+            raise ValueError(f"PseudoLabelMeter.update: unknown stage {stage!r}; the meter has {self.stages}")
+        boxes, labels, scores, off, device = self._flat(pseudo, None, "pseudo")
+        gboxes, glabels, _, goff, device = self._flat(list(gts), device, "ground-truth")
+        if len(off) != len(goff):
+            raise ValueError(f"PseudoLabelMeter.update: pseudo rows of {len(off) - 1} images, ground truth of {len(goff) - 1}")
+        if len(off) == 1:                                                               # an empty batch
+            return
+        if not (boxes.device == gboxes.device == labels.device == glabels.device == device):
+            raise ValueError("PseudoLabelMeter.update: the pseudo rows and the ground truth lie on different devices")
+        counters = self._state(device)[self.stages.index(stage)]
+        C = self.num_classes
+        if device.type != "cuda":
+            _pseudo_quality_host(boxes, labels, scores, off, gboxes, glabels, goff, C, self.iou_thresh, counters)
+            return
+        host = np.array([off, goff], np.int32)
+        table = K.host_table(host.view(np.uint8).reshape(-1), device).view(torch.int32).view(2, len(off))      # ONE pinned upload
+        K.pseudo_quality(boxes, labels, scores, table[0], gboxes, glabels, table[1], (host[0], host[1]), C, self.iou_thresh, counters)
+
+    def merge(self, group=None):
+        """All-reduce of the counters: afterwards every rank summarizes the whole run.  A no-op without an initialised process group; a
+        rank that saw no batch takes part with zeros."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        if self._counters is None:
+            self._state(torch.device("cuda" if dist.get_backend(group) == "nccl" else "cpu"))
+        dist.all_reduce(self._counters, op=dist.ReduceOp.SUM, group=group)
+
+    def counters(self):
+        """The raw state as a CPU tensor int64 [stages, 10, C + 1] (zeros before the first update): ONE copy."""
+        if self._counters is None:
+            return torch.zeros((len(self.stages), len(K.PSEUDO_QUALITY_COUNTERS), self.num_classes + 1), dtype=torch.int64)
+        return self._counters.cpu()
+
+    def summarize(self):
+        """-> {stage: {'corloc', 'any_hit', 'precision', 'recall', 'mean_iou': fp64 [C] (NaN where the denominator is 0); 'mean_corloc',
+        'mean_any_hit', 'mean_precision', 'mean_recall', 'mean_mean_iou': floats over the classes that have a value (NaN if none has);
+        'counters': int64 [10, C] by K.PSEUDO_QUALITY_COUNTERS, 'dropped_rows', 'dropped_gts': ints}} - CPU tensors; one copy."""
+        C = self.num_classes
+        all_counters = self.counters().numpy()
+        out = {}
+        for s, stage in enumerate(self.stages):
+            c = all_counters[s, :, :C]
+            f = c.astype(np.float64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                per = {"corloc": f[1] / f[0], "any_hit": f[2] / f[0], "precision": f[5] / f[4], "recall": f[8] / f[7],
+                       "mean_iou": f[9] / float(K.PSEUDO_QUALITY_IOU_SCALE) / (f[4] - f[6])}
+            for name, den in (("corloc", c[0]), ("any_hit", c[0]), ("precision", c[4]), ("recall", c[7]), ("mean_iou", c[4] - c[6])):
+                per[name] = np.where(den > 0, per[name], np.nan)
+            res = {k: torch.from_numpy(v.copy()) for k, v in per.items()}
+            for k, v in per.items():
+                have = ~np.isnan(v)
+                res["mean_" + k] = float(np.mean(v[have])) if have.any() else float("nan")
+            res["counters"] = torch.from_numpy(c.copy())
+            res["dropped_rows"], res["dropped_gts"] = int(all_counters[s, 4, C]), int(all_counters[s, 7, C])
+            out[stage] = res
+        return out
+
+    def __str__(self):
+        out = self.summarize()
+        return "\n".join("Pseudo labels [{}]: CorLoc {:.4f}  precision {:.4f}  recall {:.4f}  mean IoU {:.4f}".format(
+            stage, r["mean_corloc"], r["mean_precision"], r["mean_recall"], r["mean_mean_iou"]) for stage, r in out.items())

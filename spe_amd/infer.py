@@ -265,3 +265,20 @@ def refine_targets(outputs, classes):
     else:
         scores, queries, picked = _refine_pick_host(prob, boxes, table)
     return {"scores": scores, "labels": table.labels, "boxes": picked, "queries": queries, "offsets": table.off}
+
+
+# ---- pseudo labels as detector output (reference engine_loc.py:204-220) --------------------------------------------------------------------
+@torch.no_grad()
+def pseudo_label_to_det_out(pseudo_label, target_sizes):
+    """Same signature and result as engine_loc.py:204-220: per image {'scores', 'labels', 'boxes'} with the pseudo boxes as xyxy in absolute
+    pixels - box_cxcywh_to_xyxy, clamp(min=0), times [w, h, w, h] of target_sizes [B, 2] (h, w) - and a score of 1 for every row, in the
+    labels' INTEGER dtype, as the reference has it.  The list goes into VOCDetectionMeter.update() like a detector's; an ATen composition,
+    no kernel.  For counting hits while training runs see evalmetrics.PseudoLabelMeter."""
+    assert target_sizes.shape[1] == 2
+    results = []
+    for p, size in zip(pseudo_label, target_sizes):
+        img_h, img_w = size
+        scale = torch.stack([img_w, img_h, img_w, img_h], dim=0).unsqueeze(0)
+        boxes = box_ops.box_cxcywh_to_xyxy(p["boxes"]).clamp(min=0) * scale
+        results.append({"scores": torch.ones_like(p["labels"]), "labels": p["labels"], "boxes": boxes})
+    return results

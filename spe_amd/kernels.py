@@ -1883,6 +1883,33 @@ def refine_pick(prob, pred_boxes, cls, cls_off, host=None, out=None):
     return scores, queries, boxes
 
 
+# ---- pseudo-label quality (csrc/pseudo_quality.hip) ---------------------------------------------------------------
+PSEUDO_QUALITY_MAX_ROWS = 1024      # pseudo rows and ground-truth rows per image spe_pseudo_quality takes (-2 beyond)
+PSEUDO_QUALITY_COUNTERS = ("pairs", "pairs_lead_hit", "pairs_any_hit", "pairs_empty", "rows", "rows_hit", "rows_orphan", "gts", "gts_covered",
+                           "iou_q")
+PSEUDO_QUALITY_IOU_SCALE = 1 << 20  # counter 9 holds the best IoUs in units of 2^-20
+
+
+def pseudo_quality(boxes, labels, scores, off, gboxes, glabels, goff, host, C, iou_thresh, counters):
+    """Pseudo rows (boxes fp32 [T, 4] normalised cxcywh, labels int64 [T], scores fp32 [T] or None, off int32 [B + 1]) and ground-truth
+    rows (gboxes [G, 4], glabels [G], goff [B + 1]) of one batch, all on the device; host: the two offset vectors as int32 numpy arrays
+    (the library checks the limits on them).  Adds into counters, int64 [10, C + 1] on the device (PSEUDO_QUALITY_COUNTERS; the rules are
+    in include/spe_hip.h).  One launch, nothing is read back."""
+    _check_typed("pseudo_quality", ((boxes, torch.float32), (labels, torch.int64), (off, torch.int32), (gboxes, torch.float32),
+                                    (glabels, torch.int64), (goff, torch.int32), (counters, torch.int64)))
+    if scores is not None:
+        _check_typed("pseudo_quality", ((scores, torch.float32),))
+    import numpy as np
+    ho, hg = (np.ascontiguousarray(h, dtype=np.int32) for h in host)
+    T, G, B = labels.numel(), glabels.numel(), off.numel() - 1
+    if boxes.numel() != 4 * T or gboxes.numel() != 4 * G or (scores is not None and scores.numel() != T) or goff.numel() != B + 1 \
+            or ho.size != B + 1 or hg.size != B + 1 or counters.numel() != len(PSEUDO_QUALITY_COUNTERS) * (C + 1):
+        raise ValueError("pseudo_quality: inconsistent shapes")
+    _call("spe_pseudo_quality", _p(boxes), _p(labels), _p(scores), _p(off), _p(gboxes), _p(glabels), _p(goff), ho.ctypes.data,
+          hg.ctypes.data, B, T, G, int(C), float(iou_thresh), _p(counters), _st())
+    return counters
+
+
 def pos_sine(mask_bool, dim_t, npf, scale, eps, normalize):
     """mask [B,h,w] bool (True = padded) -> [B,h,w,2*npf] fp32 sine position features (csrc/misc.hip)."""
     B, h, w = mask_bool.shape
