@@ -49,7 +49,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_cls_ap / spe_cls_ap_workspace (the multi-label classification AP of the image-label logits on the device)
  * spe_cam_targets / spe_refine_pick (the training targets assembled on the device: CAM boxes -> target rows, the stage k+1 picks in one launch)
  * spe_pseudo_quality (the quality of the pseudo labels against the loader's ground truth: per-class counters kept on the device)
- * - 115 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
+ * spe_proposal_recall (recall-at-k and ceiling of a stage's Q query boxes against the loader's ground truth: per-class counters kept on the device)
+ * - 116 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -689,6 +690,33 @@ int spe_refine_pick(const float* prob, const float* pred_boxes, const int* cls, 
 int spe_pseudo_quality(const float* boxes, const long* labels, const float* scores, const int* off, const float* gboxes,
                        const long* glabels, const int* goff, const int* off_host, const int* goff_host, int B, int T, int G, int C,
                        float iou_thresh, long* counters, spe_stream_t stream);
+
+/* ---- proposal recall on the device (csrc/proposal_recall.hip): are the Q query boxes of a stage on the objects, or
+ * is the pick among them wrong?  spe_pseudo_quality scores the one query per (image, class) that PostProcessRefine picks; this scores every
+ * ground-truth row against ALL Q queries of its image.  The reference has no route to these numbers (its evaluator sees NMS survivors).
+ * spe_proposal_recall: prob [B][Q][Kc] (the sigmoid of the logits) and boxes [B][Q][4] normalised cxcywh of one stage; ground truth of the
+ *   batch concatenated, image b owning rows goff[b] .. goff[b+1] (int32 [B + 1], device; once more on the HOST as goff_host, required):
+ *   gboxes [G][4] normalised cxcywh, glabels [G] (int64).  thr [T] and ks [K]: HOST tables, 1 <= T, K <= 8, thr finite and strictly
+ *   ascending, ks >= 1 and strictly ascending (values above Q are allowed); they travel by value in the launch arguments.
+ *   counters: int64 [2 + T + T * K][C + 1], ACCUMULATED in place: row 0 gts, 1 iou_q, 2 + t ceil[t], 2 + T + t * K + k hit[t][k].
+ *   Rules, for a ground-truth row g of image b with label c:
+ *   1. c outside [0, min(C, Kc)): gts[C] += 1 and nothing else.  Otherwise gts[c] += 1.
+ *   2. iou[q] for all Q queries of image b: spe_pseudo_quality's IoU (box_iou on box_cxcywh_to_xyxy of both rows in fp32, one rounding per
+ *      operation; csrc/box_iou_f32.h).
+ *   3. best = the maximum over the non-NaN iou[q]; finite and > 0: iou_q[c] += llrint(min(best, 1) * 2^20).
+ *   4. Per threshold t, S_t = { q : iou[q] > thr[t] } (strict; a NaN never covers).  Empty: nothing is counted for t.  Otherwise
+ *      ceil[t][c] += 1; lead = the first element of S_t in class c's order of the image's queries by prob[b][q][c] - a NaN before every
+ *      number, NaNs among themselves by lower q, larger values first, equal values (+0.0 == -0.0) by lower q: a total order whose first
+ *      element is torch.max's and spe_refine_pick's pick; r = the number of queries of the image that precede lead in that order;
+ *      hit[t][k][c] += 1 for every k with r < ks[k].
+ *   One workgroup of 256 threads per image, the image's boxes as corners and areas in LDS, one wave per ground-truth row, O(T * Q) per
+ *   row; integer atomics only: bitwise reproducible.  Asynchronous, nothing is read back.  B = 0 or G = 0: status 0, nothing launched.
+ *   -2: Q > 1024 (the LDS staging).  -3: B or G < 0, Q, Kc or C < 1, T or K outside [1, 8], a table that is not strictly ascending, a
+ *   threshold that is not finite, a cut-off < 1, host offsets that do not start at 0, descend or do not end at G, a NULL goff_host, thr,
+ *   ks or counters, a NULL device buffer when something is launched.  All of it is checked before anything is launched. */
+int spe_proposal_recall(const float* prob, const float* boxes, const float* gboxes, const long* glabels, const int* goff,
+                        const int* goff_host, int B, int Q, int Kc, int G, int C, const float* thr, int T, const int* ks, int K,
+                        long* counters, spe_stream_t stream);
 
 /* ---- PASCAL VOC detection metrics (reference engine_loc.py:176-197, datasets/voc_eval.py, datasets/dis_eval.py; csrc/voc_eval.hip).
  * All arithmetic is fp64 in numpy's operation order, compiled without FMA contraction: with equal inputs the overlaps, and so every

@@ -36,7 +36,9 @@ EXTRA_FLAGS = {"attn_flash_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # train_targets.hip restates the host's fp32 box normalisation: an add, a halving and a division, each rounded on its own
                "train_targets.hip": ["-ffp-contract=off"],
                # pseudo_quality.hip restates box_iou's fp32 composition: products, sums and the division each rounded on their own, so iou > threshold decides alike
-               "pseudo_quality.hip": ["-ffp-contract=off"]}
+               "pseudo_quality.hip": ["-ffp-contract=off"],
+               # proposal_recall.hip scores every query box with the same fp32 box_iou (box_iou_f32.h): iou == threshold must not hit, on the device as on the host
+               "proposal_recall.hip": ["-ffp-contract=off"]}
 
 
 def flags_for(src):

@@ -14,36 +14,16 @@
 //   Integer atomics only: the counters are a function of the input alone.
 //
 // The IoU is util.box_ops.box_iou on box_cxcywh_to_xyxy of both rows in fp32, operation for operation (corners, areas, max / min,
-// clamp(min=0), inter, (area1 + area2) - inter, the division).  This file is compiled without FMA contraction (spe_amd/build.py) and
-// spells the arithmetic with the _rn intrinsics besides: one rounding per operation.
+// clamp(min=0), inter, (area1 + area2) - inter, the division): box_iou_f32.h, shared with proposal_recall.hip.  This file is compiled
+// without FMA contraction (spe_amd/build.py) and the header spells the arithmetic with the _rn intrinsics besides: one rounding per operation.
 #include "common.h"
+#include "box_iou_f32.h"
 
 #define PQ_THREADS 256
 #define PQ_MAX_ROWS 1024           // pseudo rows and ground-truth rows per image (-2 beyond)
 #define PQ_COUNTERS 10
 
 enum { PQ_PAIRS = 0, PQ_PAIRS_LEAD_HIT, PQ_PAIRS_ANY_HIT, PQ_PAIRS_EMPTY, PQ_ROWS, PQ_ROWS_HIT, PQ_ROWS_ORPHAN, PQ_GTS, PQ_GTS_COVERED, PQ_IOU_Q };
-
-// torch.max / torch.min of two numbers: a NaN on either side is the result
-__device__ __forceinline__ float pq_max(float a, float b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
-__device__ __forceinline__ float pq_min(float a, float b) { return a != a ? a : (b != b ? b : (a < b ? a : b)); }
-// clamp(min=0): a NaN stays
-__device__ __forceinline__ float pq_clamp0(float v) { return v < 0.f ? 0.f : v; }
-
-// box_cxcywh_to_xyxy: [cx - 0.5 w, cy - 0.5 h, cx + 0.5 w, cy + 0.5 h]
-__device__ __forceinline__ float4 pq_corners(const float* __restrict__ row) {
-    const float cx = row[0], cy = row[1], hw = __fmul_rn(0.5f, row[2]), hh = __fmul_rn(0.5f, row[3]);
-    return make_float4(__fsub_rn(cx, hw), __fsub_rn(cy, hh), __fadd_rn(cx, hw), __fadd_rn(cy, hh));
-}
-
-__device__ __forceinline__ float pq_area(float4 b) { return __fmul_rn(__fsub_rn(b.z, b.x), __fsub_rn(b.w, b.y)); }
-
-__device__ __forceinline__ float pq_iou(float4 a, float aa, float4 b, float ab) {
-    const float w = pq_clamp0(__fsub_rn(pq_min(a.z, b.z), pq_max(a.x, b.x)));
-    const float h = pq_clamp0(__fsub_rn(pq_min(a.w, b.w), pq_max(a.y, b.y)));
-    const float inter = __fmul_rn(w, h);
-    return __fdiv_rn(inter, __fsub_rn(__fadd_rn(aa, ab), inter));
-}
 
 __device__ __forceinline__ void pq_add(long* counters, int C, int k, int c, long v) {
     atomicAdd(reinterpret_cast<unsigned long long*>(counters + (size_t)k * (C + 1) + c), (unsigned long long)v);
@@ -106,8 +86,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pseudo_quality_kernel(const float*
             pq_add(counters, C, PQ_ROWS_HIT, cls, 1);
         }
         if (best > 0.f && best < INFINITY) {
-            const long q = __float2ll_rn(__fmul_rn(best < 1.f ? best : 1.f, 1048576.f));      // a power of two: the product is exact
-            pq_add(counters, C, PQ_IOU_Q, cls, q);
+            pq_add(counters, C, PQ_IOU_Q, cls, pq_iou_quantum(best));
         }
     }
     __syncthreads();

@@ -104,7 +104,7 @@ def apply_curriculum_coco(weight_dict, epoch):
 
 
 def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, device, epoch, max_norm, args, postprocessors, criterion_refine,
-                     pseudo_meter=None):
+                     pseudo_meter=None, proposal_meter=None):
     """The loop of both public entries; `curriculum(weight_dict, epoch)` is what differs between them.
 
     pseudo_meter: an evalmetrics.PseudoLabelMeter with the stages 'cam', 'rf_1' .. 'rf_<num_refines>' (DESIGN.md section 8o).  Every
@@ -114,6 +114,12 @@ def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, devic
     pseudo_<stage>_corloc / _precision / _recall / _mean_iou.  The rows are scored in the frame the criterion receives them: CAM rows
     normalised by the padded canvas (with the (H, W) -> dsize transposition of camboxes._pseudo_labels), ground truth by the image's own
     size - on fixed square inputs the same frame, elsewhere the mismatch the criterion trains on.  None: nothing of it.
+
+    proposal_meter: an evalmetrics.ProposalRecallMeter with the stages 's0' .. 's<num_refines>' (DESIGN.md section 8p).  Every batch scores
+    ALL query boxes of every stage of `outputs`, 0 included, against the same ground-truth rows: the sigmoid and one launch per (step,
+    stage), no host read.  After the loop the meter is merged and printed, and the statistics gain prop_s<rf>_recall_at_<k> for every k
+    of the meter, prop_s<rf>_ceiling (both at the meter's first threshold, means over the classes with rows) and
+    prop_s<rf>_mean_best_iou.  None: nothing of it.
 
     Gradient accumulation: with a FlatAdamW whose reducer has accum_steps > 1 every iteration still does zero_grad / backward /
     finish() and is recorded in the ledger, optimizer.step() runs when finish() completed a cycle, and the micro-batches of a cycle
@@ -139,7 +145,7 @@ def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, devic
         pseudo = camboxes.pseudo_targets(outputs[0], samples, present, args.num_classes, args.cam_thr, args.multi_box_ratio)
         logits = outputs[0]["pred_logits"]
         uniq = infer.ClassTable([[c for c in cl if c < logits.shape[2]] for cl in pseudo.classes], logits.device).per_image()
-        if pseudo_meter is not None:
+        if pseudo_meter is not None or proposal_meter is not None:
             for key in ("boxes", "labels"):
                 if any(key not in t for t in targets):
                     raise ValueError(f"pseudo_meter: the loader's targets carry no {key!r} to score the pseudo labels against")
@@ -152,6 +158,9 @@ def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, devic
             pseudo_meter.update("cam", pseudo, gt)
             for rf, rows in pseudo_label_refine.items():
                 pseudo_meter.update(f"rf_{rf}", rows, gt)
+        if proposal_meter is not None:
+            for rf, out in outputs.items():
+                proposal_meter.update(f"s{rf}", out, gt)
         loss_dict = criterion(outputs[0], targets)
         for rf, out in outputs.items():
             if rf == 0:
@@ -190,21 +199,29 @@ def _train_one_epoch(curriculum, model, criterion, data_loader, optimizer, devic
             for k in ("corloc", "precision", "recall"):
                 stats[f"pseudo_{stage}_{k}"] = r["mean_" + k]
             stats[f"pseudo_{stage}_mean_iou"] = r["mean_mean_iou"]
+    if proposal_meter is not None:
+        proposal_meter.merge()
+        print(proposal_meter)
+        for stage, r in proposal_meter.summarize().items():
+            for k, v in zip(proposal_meter.ks, r["mean_recall"][0].tolist()):
+                stats[f"prop_{stage}_recall_at_{k}"] = v
+            stats[f"prop_{stage}_ceiling"] = float(r["mean_ceiling"][0])
+            stats[f"prop_{stage}_mean_best_iou"] = r["mean_mean_best_iou"]
     return stats
 
 
 def train_one_epoch_refine(model, criterion, data_loader, optimizer, device, epoch, max_norm=0, args=None, postprocessors=None,
-                           criterion_refine=None, pseudo_meter=None):
-    """engine.py:93-174 (the VOC loop).  pseudo_meter: see _train_one_epoch."""
+                           criterion_refine=None, proposal_meter=None, pseudo_meter=None):
+    """engine.py:93-174 (the VOC loop).  pseudo_meter, proposal_meter: see _train_one_epoch."""
     return _train_one_epoch(apply_curriculum, model, criterion, data_loader, optimizer, device, epoch, max_norm, args, postprocessors,
-                            criterion_refine, pseudo_meter=pseudo_meter)
+                            criterion_refine, pseudo_meter=pseudo_meter, proposal_meter=proposal_meter)
 
 
 def train_one_epoch_refine_coco(model, criterion, data_loader, optimizer, device, epoch, max_norm=0, args=None, postprocessors=None,
-                                criterion_refine=None, pseudo_meter=None):
-    """engine.py:534-613 (the loop main_coco.py:356 calls): the same body with the COCO curriculum.  pseudo_meter: see _train_one_epoch."""
+                                criterion_refine=None, proposal_meter=None, pseudo_meter=None):
+    """engine.py:534-613 (the loop main_coco.py:356 calls): the same body with the COCO curriculum.  pseudo_meter, proposal_meter: see _train_one_epoch."""
     return _train_one_epoch(apply_curriculum_coco, model, criterion, data_loader, optimizer, device, epoch, max_norm, args, postprocessors,
-                            criterion_refine, pseudo_meter=pseudo_meter)
+                            criterion_refine, pseudo_meter=pseudo_meter, proposal_meter=proposal_meter)
 
 
 # ---- evaluation loops (reference engine_loc.py:127-201, engine.py:617-724; DESIGN.md section 8k) -----------------------------------
@@ -234,7 +251,7 @@ def _coco_cat_ids(base_ds):
 
 @torch.no_grad()
 def evaluate_det_voc(model, criterion, postprocessors, data_loader, base_ds, device, output_dir, cache_dir, with_flip=False, *kargs,
-                     cls_meter=None, cls_key="x_logits", **kwargs):
+                     cls_meter=None, cls_key="x_logits", proposal_meter=None, **kwargs):
     """engine_loc.py:127-201 with the VOC meter in place of the result files: top 300, per-class NMS at 0.5, AP (VOC07 11-point unless
     use_07_metric=False is passed) and CorLoc, printed in the lines of datasets/voc_voc.py:_eval_discovery and _do_python_eval (without
     the closing banner about the MATLAB code).  base_ds: image id (t['idx']) -> {'boxes' [g,4] annotation frame, 'labels' [g],
@@ -242,8 +259,13 @@ def evaluate_det_voc(model, criterion, postprocessors, data_loader, base_ds, dev
     count from there or from num_classes= (20).  Writes no files; returns the meter's summary (the reference returns None).
     cls_meter: an evalmetrics.ClassificationAPMeter (the reference's AveragePrecisionMeter, cams_deit.py:493-574) that is fed the raw
     image-level logits outputs[cls_key] - with_flip: of the merged output - against the stacked t['label'] of every batch; after the
-    detection lines its per-class AP and the mean are printed and returned as 'cls_ap' (fp64 [C]) and 'cls_map'.  None: nothing of it."""
+    detection lines its per-class AP and the mean are printed and returned as 'cls_ap' (fp64 [C]) and 'cls_map'.  None: nothing of it.
+    proposal_meter: an evalmetrics.ProposalRecallMeter with a stage 'det' (DESIGN.md section 8p): every batch scores all query boxes of
+    the (with_flip: merged) outputs against base_ds's rows - the boxes divided by the image's [w, h, w, h] and turned into cxcywh on the
+    device, the labels as they are (a label is its logit column).  Merged and printed after the loop, its summary returned as
+    'proposals'.  None: nothing of it."""
     from .evalmetrics import VOCDetectionMeter
+    from .util.box_ops import box_xyxy_to_cxcywh
     from .util.misc import NestedTensor
     model.eval()
     criterion.eval()
@@ -255,6 +277,8 @@ def evaluate_det_voc(model, criterion, postprocessors, data_loader, base_ds, dev
     use_07_metric = bool(kwargs.get("use_07_metric", True))
     meter = VOCDetectionMeter(num_classes=C, ovthresh=0.5, file_roundtrip=True)
     gt_of = _lookup(base_ds)
+    if proposal_meter is not None and "det" not in proposal_meter.stages:
+        raise ValueError(f"proposal_meter: the evaluation loop updates the stage 'det'; the meter has {proposal_meter.stages}")
     for samples, targets in ledger.log_every(data_loader, 256, header):
         ids = [_host_id(t, "idx") for t in targets]
         samples = samples.to(device)
@@ -269,6 +293,14 @@ def evaluate_det_voc(model, criterion, postprocessors, data_loader, base_ds, dev
         sizes = torch.stack([t["image_size"].flip(0) for t in targets], dim=0)
         det = infer.detect(outputs, sizes, 300, 0.5)
         meter.update(det.padded(), [{**gt_of(i), "image_id": t["idx"].reshape(())} for i, t in zip(ids, targets)])
+        if proposal_meter is not None:
+            rows = []
+            for i, t in zip(ids, targets):
+                g = gt_of(i)
+                xyxy = torch.as_tensor(g["boxes"]).to(device=device, dtype=torch.float32).reshape(-1, 4)
+                rows.append({"boxes": box_xyxy_to_cxcywh(xyxy / t["image_size"].to(torch.float32).repeat(2)),
+                             "labels": torch.as_tensor(g["labels"]).to(device=device, dtype=torch.int64).reshape(-1)})
+            proposal_meter.update("det", outputs, rows)
         if cls_meter is not None:
             cls_meter.add(outputs[cls_key], torch.stack([t["label"] for t in targets]))      # logits, not sigmoids: no saturation ties
     meter.merge()
@@ -293,6 +325,10 @@ def evaluate_det_voc(model, criterion, postprocessors, data_loader, base_ds, dev
             print("AP (cls) for {} = {:.4f}".format(name, v))
         print("Mean AP (cls) = {:.4f}".format(cls["map"]))
         out["cls_ap"], out["cls_map"] = cls["ap"], cls["map"]
+    if proposal_meter is not None:
+        proposal_meter.merge()
+        print(proposal_meter)
+        out["proposals"] = proposal_meter.summarize()["det"]
     return out
 
 

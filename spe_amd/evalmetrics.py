@@ -1,6 +1,7 @@
 """Metrics of the SPE evaluation loops, kept on the device: the two detection meters and, at the end of the file, the multi-label
 classification AP of the image-level logits (`ClassificationAPMeter`: reference cams_deit.py:493-574; `spe_cls_ap`)
-and the one meter of the TRAINING loops, the quality of their pseudo labels (`PseudoLabelMeter`; `spe_pseudo_quality`; section 8o).
+and the meters of the TRAINING loops: the quality of their pseudo labels (`PseudoLabelMeter`; `spe_pseudo_quality`; section 8o) and the
+recall of a stage's query boxes before the pick (`ProposalRecallMeter`; `spe_proposal_recall`; section 8p).
 
 PASCAL VOC: the last step of reference
 `engine_loc.evaluate_det_voc` (engine_loc.py:176-197), i.e. `evaluate_detections` -> `voc_eval` (datasets/voc_voc.py:366-437,
@@ -874,3 +875,219 @@ class PseudoLabelMeter:
         out = self.summarize()
         return "\n".join("Pseudo labels [{}]: CorLoc {:.4f}  precision {:.4f}  recall {:.4f}  mean IoU {:.4f}".format(
             stage, r["mean_corloc"], r["mean_precision"], r["mean_recall"], r["mean_mean_iou"]) for stage, r in out.items())
+
+
+# ---- proposal recall (csrc/proposal_recall.hip) -------------------------------------------------------------------
+def _proposal_tables(who, iou_threshs, ks):
+    """The two small tables as the library wants them (fp32 thresholds, int32 cut-offs), checked: ValueError names the argument."""
+    limit = K.PROPOSAL_RECALL_MAX_TABLE
+    try:
+        thr = np.asarray(list(iou_threshs), dtype=np.float32).reshape(-1)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{who}: iou_threshs must be a sequence of numbers") from e
+    if not 1 <= thr.size <= limit or not np.all(np.isfinite(thr)) or np.any(thr[1:] <= thr[:-1]):
+        raise ValueError(f"{who}: iou_threshs must be 1 to {limit} finite, strictly ascending values (in fp32), got {list(iou_threshs)}")
+    kl = list(ks)
+    if not 1 <= len(kl) <= limit or any(int(k) != k or not 1 <= int(k) < 2 ** 31 for k in kl) or any(b <= a for a, b in zip(kl, kl[1:])):
+        raise ValueError(f"{who}: ks must be 1 to {limit} strictly ascending integers, each at least 1, got {kl}")
+    return thr, np.asarray([int(k) for k in kl], dtype=np.int32)
+
+
+def _class_order_position(p):
+    """p fp32 [Q], one class's probabilities of an image's queries -> int64 [Q]: how many queries come before each one in the class's
+    order - a NaN before every number, larger values first, equal values (and NaNs among themselves) by lower q.  Three explicit sort
+    keys, the query index among them: nothing rests on a sort's tie behaviour."""
+    p = p.numpy()
+    nan = np.isnan(p)
+    order = np.lexsort((np.arange(p.size), -np.where(nan, np.float32(0), p), ~nan))          # the LAST key is the primary one
+    pos = np.empty(p.size, np.int64)
+    pos[order] = np.arange(p.size)
+    return torch.from_numpy(pos)
+
+
+def _proposal_recall_host(prob, boxes, gboxes, glabels, goff, C, thr, ks, counters):
+    """kernels.proposal_recall on CPU tensors, composed of torch / numpy operations per image: box_iou on the corners of both sides (fp32,
+    elementwise: one rounding per operation), the class's order as positions, integer counts added into `counters` [2 + T + T * K, C + 1]."""
+    from .util import box_ops
+    B, Q, Kc = prob.shape
+    T, Kn = len(thr), len(ks)
+    limit = min(C, Kc)
+    thr_t = torch.from_numpy(np.asarray(thr, np.float32))
+    ks_t = torch.from_numpy(np.asarray(ks, np.int64))
+    for b in range(B):
+        g = slice(goff[b], goff[b + 1])
+        labels = glabels[g]
+        valid = (labels >= 0) & (labels < limit)
+        counters[0].index_add_(0, torch.where(valid, labels, torch.full_like(labels, C)), torch.ones_like(labels))
+        if not bool(valid.any()):
+            continue
+        labels = labels[valid]
+        iou = box_ops.box_iou(box_ops.box_cxcywh_to_xyxy(gboxes[g][valid]), box_ops.box_cxcywh_to_xyxy(boxes[b]))[0]          # [g, Q]
+        best = torch.where(torch.isnan(iou), torch.full_like(iou, float("-inf")), iou).max(dim=1).values
+        counted = (best > 0) & torch.isfinite(best)
+        q = torch.round(best[counted].clamp(max=1) * float(K.PROPOSAL_RECALL_IOU_SCALE)).to(torch.int64)      # half to even, like llrint
+        counters[1].index_add_(0, labels[counted], q)
+        for c in torch.unique(labels).tolist():
+            rows = labels == c
+            pos = _class_order_position(prob[b, :, c])
+            one = torch.tensor([c])
+            for t in range(T):
+                cover = iou[rows] > thr_t[t]                                               # strict; a NaN never covers
+                r = torch.where(cover, pos[None, :], torch.full_like(pos, Q)[None, :]).min(dim=1).values       # the position of the lead
+                r = r[r < Q]
+                counters[2 + t].index_add_(0, one, torch.tensor([r.numel()]))
+                hits = (r[:, None] < ks_t[None, :]).sum(dim=0)
+                counters[2 + T + t * Kn:2 + T + (t + 1) * Kn, c] += hits
+    return counters
+
+
+class ProposalRecallMeter:
+    """Are the sparse proposals of a stage on the objects, or is the pick among them wrong?  Every ground-truth row is scored against ALL
+    Q query boxes of its image and stage, counted while training runs: per class and stage the recall-at-k curve under the class's own
+    ordering of the queries (k = 1 is exactly PostProcessRefine's pick) and the ceiling with all Q queries.  ceiling - recall@1 is the
+    selection gap: a low ceiling is a localisation failure, a high ceiling with a low recall@1 a selection failure.
+
+        m = ProposalRecallMeter(num_classes=21, stages=["s0", "s1", "s2"], iou_threshs=(0.5, 0.75), ks=(1, 10, 100))
+        m.update("s0", outputs[0], gts)    # per batch and stage: the sigmoid and one launch on the device, nothing read on the host
+        m.merge()                          # once, when the images were split over ranks: an all-reduce of the counters
+        out = m.summarize()                # {stage: {'recall' fp64 [T, K, C], 'ceiling' [T, C], 'selection_gap' [T, C], 'mean_best_iou' [C], ...}}
+        print(m)                           # one line per stage
+
+    outputs: {'pred_logits' [B, Q, Kc], 'pred_boxes' [B, Q, 4] normalised cxcywh}; the queries are ordered by pred_logits.sigmoid(), bitwise
+    the probabilities infer.refine_targets picks on, saturation ties included.  gts: per image {'boxes' [g, 4] normalised cxcywh, 'labels'
+    [g]}, the loader's target rows.  num_classes = C: labels lie in [0, min(C, Kc)) and a label is its logit column.
+
+    Rules (the package's own; csrc/proposal_recall.hip).  IoU: box_iou on box_cxcywh_to_xyxy of both rows in fp32, PseudoLabelMeter's.  A
+    ground-truth row with a label outside [0, min(C, Kc)) is counted ('dropped_gts') and takes no further part.  Best IoU of a row: the
+    maximum over its non-NaN IoUs with the Q queries of its image; capped at 1 and rounded to a multiple of 2^-20 (not finite or not
+    positive: 0) it joins an integer sum.  Per threshold the covering set is the queries with IoU > threshold (strict; a NaN never
+    covers); a row with a non-empty set counts for the ceiling, and its lead is the set's first query in its class's order: a NaN
+    probability before every number, larger values first, equal values and NaNs among themselves by lower query - torch.max's and
+    spe_refine_pick's pick comes first.  The row hits at k when fewer than k queries of the image precede the lead.  Per class:
+    recall[t][k] = hits / rows, ceiling[t] = rows with a covering query / rows, selection_gap[t] = ceiling[t] - recall[t][0],
+    mean_best_iou = the mean best IoU.  A class without ground-truth rows is NaN and takes no part in that stage's mean_* values
+    (ClassificationAPMeter's rule).  Every number is a function of the input alone.
+
+    The boxes are scored in the frame the criterion receives them; the meter does not rescale (PseudoLabelMeter's statement).
+
+    The state is int64 [stages, 2 + T + T * K, C + 1] on the device of the first update.  CUDA tensors take spe_proposal_recall (one
+    launch per update, the offsets in one pinned upload, at most 1024 queries); CPU tensors take a torch / numpy composition of the same
+    rules."""
+
+    def __init__(self, num_classes, stages, iou_threshs=(0.5, 0.75), ks=(1, 10, 100)):
+        self.num_classes, self.stages = int(num_classes), [str(s) for s in stages]
+        if self.num_classes < 1:
+            raise ValueError("ProposalRecallMeter: num_classes must be at least 1")
+        if len(set(self.stages)) != len(self.stages) or not self.stages:
+            raise ValueError("ProposalRecallMeter: stages must be distinct names, at least one")
+        self._thr, self._ks = _proposal_tables("ProposalRecallMeter", iou_threshs, ks)
+        self.iou_threshs, self.ks = tuple(float(t) for t in self._thr), tuple(int(k) for k in self._ks)
+        self.rows = K.proposal_recall_counters(len(self.iou_threshs), len(self.ks))
+        self.reset()
+
+    def reset(self):
+        self._counters = None              # int64 [S, 2 + T + T * K, C + 1] on the device of the first update
+
+    def _shape(self):
+        return (len(self.stages), len(self.rows), self.num_classes + 1)
+
+    def _state(self, device):
+        if self._counters is None:
+            self._counters = torch.zeros(self._shape(), dtype=torch.int64, device=device)
+        elif self._counters.device != device:
+            raise ValueError(f"ProposalRecallMeter: tensors on {device}, earlier updates on {self._counters.device}")
+        return self._counters
+
+    @torch.no_grad()
+    def update(self, stage, outputs, gts):
+        who = "ProposalRecallMeter.update"
+        if stage not in self.stages:
+            raise ValueError(f"{who}: unknown stage {stage!r}; the meter has {self.stages}")
+        for k in ("pred_logits", "pred_boxes"):
+            if k not in outputs:
+                raise ValueError(f"{who}: outputs have no {k!r}")
+        logits, boxes = outputs["pred_logits"].detach(), outputs["pred_boxes"].detach()
+        if logits.dim() != 3 or boxes.shape != logits.shape[:2] + (4,):
+            raise ValueError(f"{who}: outputs must hold pred_logits [B, Q, Kc] and pred_boxes [B, Q, 4], got {tuple(logits.shape)} and "
+                             f"{tuple(boxes.shape)}")
+        B, Q, Kc = logits.shape
+        gts = list(gts)
+        if len(gts) != B:
+            raise ValueError(f"{who}: outputs of {B} images, gts of {len(gts)}")
+        if B == 0:                                                                      # an empty batch
+            return
+        if Q < 1 or Kc < 1 or Q > K.PROPOSAL_RECALL_MAX_Q:
+            raise ValueError(f"{who}: outputs with 1 to {K.PROPOSAL_RECALL_MAX_Q} queries and at least one class expected, got {tuple(logits.shape)}")
+        device = logits.device
+        goff = [0]
+        for i, r in enumerate(gts):
+            for k in ("boxes", "labels"):
+                if k not in r:
+                    raise ValueError(f"{who}: gts of image {i} have no {k!r}")
+            goff.append(goff[-1] + r["labels"].shape[0])
+        gboxes = PseudoLabelMeter._cat([r["boxes"] for r in gts], torch.float32, (4,), device)
+        glabels = PseudoLabelMeter._cat([r["labels"] for r in gts], torch.int64, (), device)
+        if gboxes.shape[0] != goff[-1]:
+            raise ValueError(f"{who}: gts hold {goff[-1]} labels and {gboxes.shape[0]} boxes")
+        if not (boxes.device == gboxes.device == glabels.device == device):
+            raise ValueError(f"{who}: outputs and gts lie on different devices")
+        counters = self._state(device)[self.stages.index(stage)]
+        prob = logits.to(torch.float32).sigmoid()                                       # fp32 logits: the one ATen launch
+        boxes = boxes.to(torch.float32).contiguous()
+        if device.type != "cuda":
+            _proposal_recall_host(prob, boxes, gboxes, glabels, goff, self.num_classes, self._thr, self._ks, counters)
+            return
+        host = np.array(goff, np.int32)
+        table = K.host_table(host.view(np.uint8), device).view(torch.int32)             # ONE pinned upload
+        K.proposal_recall(prob, boxes, gboxes, glabels, table, host, self.num_classes, self._thr, self._ks, counters)
+
+    def merge(self, group=None):
+        """All-reduce of the counters: afterwards every rank summarizes the whole run.  A no-op without an initialised process group; a
+        rank that saw no batch takes part with zeros."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        if self._counters is None:
+            self._state(torch.device("cuda" if dist.get_backend(group) == "nccl" else "cpu"))
+        dist.all_reduce(self._counters, op=dist.ReduceOp.SUM, group=group)
+
+    def counters(self):
+        """The raw state as a CPU tensor int64 [stages, 2 + T + T * K, C + 1] (zeros before the first update): ONE copy."""
+        if self._counters is None:
+            return torch.zeros(self._shape(), dtype=torch.int64)
+        return self._counters.cpu()
+
+    def summarize(self):
+        """-> {stage: {'recall' fp64 [T, K, C], 'ceiling' [T, C], 'selection_gap' [T, C] (ceiling - recall at ks[0]), 'mean_best_iou' [C] - NaN
+        for a class without ground-truth rows; 'mean_recall' fp64 [T, K], 'mean_ceiling' [T], 'mean_selection_gap' [T], 'mean_mean_best_iou'
+        float: over the classes that have rows (NaN if none has); 'gts' int64 [C], 'counters' int64 [2 + T + T * K, C] by self.rows,
+        'dropped_gts' int}} - CPU tensors; one copy."""
+        C, T, Kn = self.num_classes, len(self.iou_threshs), len(self.ks)
+        all_counters = self.counters().numpy()
+        out = {}
+        for s, stage in enumerate(self.stages):
+            c = all_counters[s, :, :C]
+            gts = c[0]
+            have = gts > 0
+            den = np.where(have, gts, 1).astype(np.float64)
+
+            def per_class(v):
+                return np.where(have, v.astype(np.float64) / den, np.nan)
+
+            per = {"recall": per_class(c[2 + T:].reshape(T, Kn, C)), "ceiling": per_class(c[2:2 + T]),
+                   "mean_best_iou": per_class(c[1]) / float(K.PROPOSAL_RECALL_IOU_SCALE)}
+            per["selection_gap"] = per["ceiling"] - per["recall"][:, 0]
+            res = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in per.items()}
+            for k, v in per.items():
+                mean = np.array([row[have].mean() if have.any() else np.nan for row in v.reshape(-1, C)]).reshape(v.shape[:-1])     # row by row: one summation order
+                res["mean_" + k] = float(mean) if mean.ndim == 0 else torch.from_numpy(np.ascontiguousarray(mean))
+            res["gts"], res["counters"] = torch.from_numpy(gts.copy()), torch.from_numpy(c.copy())
+            res["dropped_gts"] = int(all_counters[s, 0, C])
+            out[stage] = res
+        return out
+
+    def __str__(self):
+        out = self.summarize()
+        return "\n".join("Proposals [{}] IoU > {:g}: {}  ceiling {:.4f}".format(
+            stage, self.iou_threshs[0], "  ".join("recall@{} {:.4f}".format(k, v) for k, v in zip(self.ks, r["mean_recall"][0].tolist())),
+            float(r["mean_ceiling"][0])) for stage, r in out.items())

@@ -1910,6 +1910,39 @@ def pseudo_quality(boxes, labels, scores, off, gboxes, glabels, goff, host, C, i
     return counters
 
 
+# ---- proposal recall (csrc/proposal_recall.hip) -------------------------------------------------------------------
+PROPOSAL_RECALL_MAX_Q = 1024        # queries per image spe_proposal_recall takes (-2 beyond: the LDS staging)
+PROPOSAL_RECALL_MAX_TABLE = 8       # IoU thresholds, and cut-offs k
+PROPOSAL_RECALL_IOU_SCALE = 1 << 20  # counter 1 holds the best IoUs in units of 2^-20
+
+
+def proposal_recall_counters(T, K):
+    """The names of the 2 + T + T * K counter rows of spe_proposal_recall for T thresholds and K cut-offs, in row order."""
+    return ("gts", "iou_q") + tuple(f"ceil[{t}]" for t in range(T)) + tuple(f"hit[{t}][{k}]" for t in range(T) for k in range(K))
+
+
+def proposal_recall(prob, boxes, gboxes, glabels, goff, host, C, iou_threshs, ks, counters):
+    """prob fp32 [B, Q, Kc] (the sigmoid of the logits) and boxes fp32 [B, Q, 4] normalised cxcywh of one stage; the ground-truth rows of the
+    batch (gboxes [G, 4], glabels int64 [G], goff int32 [B + 1]), all on the device; host: goff as an int32 numpy array (the library checks
+    it).  iou_threshs / ks: host sequences of 1 .. 8 strictly ascending values.  Adds into counters, int64 [2 + T + T * K, C + 1] on the
+    device (proposal_recall_counters; the rules are in include/spe_hip.h).  One launch, nothing is read back."""
+    _check_typed("proposal_recall", ((prob, torch.float32), (boxes, torch.float32), (gboxes, torch.float32), (glabels, torch.int64),
+                                     (goff, torch.int32), (counters, torch.int64)))
+    import numpy as np
+    hg = np.ascontiguousarray(host, dtype=np.int32)
+    thr, kk = np.ascontiguousarray(iou_threshs, dtype=np.float32).reshape(-1), np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+    if prob.dim() != 3:
+        raise ValueError(f"proposal_recall: prob must be [B, Q, Kc], got {tuple(prob.shape)}")
+    B, Q, Kc = prob.shape
+    G, T, Kn = glabels.numel(), thr.size, kk.size
+    if boxes.shape != (B, Q, 4) or gboxes.numel() != 4 * G or goff.numel() != B + 1 or hg.size != B + 1 \
+            or counters.numel() != (2 + T + T * Kn) * (int(C) + 1):
+        raise ValueError("proposal_recall: inconsistent shapes")
+    _call("spe_proposal_recall", _p(prob), _p(boxes), _p(gboxes), _p(glabels), _p(goff), hg.ctypes.data, B, Q, Kc, G, int(C),
+          thr.ctypes.data, T, kk.ctypes.data, Kn, _p(counters), _st())
+    return counters
+
+
 def pos_sine(mask_bool, dim_t, npf, scale, eps, normalize):
     """mask [B,h,w] bool (True = padded) -> [B,h,w,2*npf] fp32 sine position features (csrc/misc.hip)."""
     B, h, w = mask_bool.shape
