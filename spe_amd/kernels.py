@@ -3,8 +3,10 @@
 Every function takes CUDA fp32 tensors, allocates its outputs with torch (device memory is
 PyTorch's job on this path) and enqueues the kernel on torch's current HIP stream.
 """
+import collections
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -348,8 +350,38 @@ def gemm_plan(M, N, K, lda, ldb, ldc, transA=False, transB=False, batch0=1, batc
 # fp32-operand kernel.
 LINEAR16 = True              # module attributes (tools/error_budget.py and the tests flip them), not environment knobs
 LINEAR16_MIN_ROWS = 128
-_W16 = {}        # id(W) -> (weakref, version, epoch, W16 [N,K], W16T [K,N], W16lo (bf16 low part or IEEE fp16 copy, or None))
+_W16 = {}        # (address, rows, cols) of a weight -> its WeightCopies
 _W16_EPOCH = 0   # bumped by writers that bypass autograd's version counters (spe_amd.optim.FlatAdamW)
+KIND_LO, KIND_F16 = "lo", "f16"       # what the second 16-bit copy of an operand is: the bf16 low part of the split, or the IEEE fp16 copy
+
+
+def _kind(second):
+    """What a record's second copy is - None, KIND_LO or KIND_F16: read off its dtype here, when the record is made, and nowhere else."""
+    return None if second is None else {torch.bfloat16: KIND_LO, torch.float16: KIND_F16}[second.dtype]
+
+
+class WeightCopies:
+    """The cached 16-bit copies of a weight [N, K] - or of a stack of weights sharing an input (bias: their stacked fp32 biases): w16 [N, K]
+    and w16T [K, N] in bf16, and `second` [N, K] of `kind` None (no second copy), KIND_LO (bf16(W - w16)) or KIND_F16 (the operand of a
+    single-term fp16 product; the fp16 stacks hold nothing else).  owners: weak references to the tensors that own the storage; versions:
+    their version counters, then the biases'; epoch: _W16_EPOCH - both as of the conversion; shape: of every copy but w16T.  _copies_state
+    judges a record."""
+    __slots__ = ("owners", "versions", "epoch", "w16", "w16T", "second", "kind", "bias", "shape")
+
+    def __init__(self, Ws, w16, w16T, second, bias=None, bias_versions=()):
+        owners = [W._base if W._base is not None else W for W in Ws]
+        self.owners = tuple(weakref.ref(o) for o in owners)
+        self.versions, self.epoch = (*[o._version for o in owners], *bias_versions), _W16_EPOCH
+        self.w16, self.w16T, self.second, self.bias = w16, w16T, second, bias
+        self.kind, self.shape = _kind(second), (second if w16 is None else w16).shape
+
+
+class ActCopies:
+    """The 16-bit copies the activation `t` carries (attribute _spe16, see attach16): x16 [R, K] in bf16, second / kind as above."""
+    __slots__ = ("version", "x16", "second", "kind")
+
+    def __init__(self, t, x16, second=None):
+        self.version, self.x16, self.second, self.kind = t._version, x16, second, _kind(second)
 
 
 def weights_changed():
@@ -413,7 +445,8 @@ def cvt_bf16(x2, want=True, wantT=False, ldt=None, colsum_out=None, act_aux=None
     return out, outT
 
 
-_W16_TABLE = None      # (signature, device job table, njobs, total tiles) of the last batched refresh
+RefreshTable = collections.namedtuple("RefreshTable", "sig table njobs tiles")     # signature, device job table, jobs, total tiles
+_W16_TABLE = None      # the RefreshTable of the last batched refresh
 _W16_REFRESHED = -1    # epoch of the last batched refresh
 
 
@@ -423,40 +456,57 @@ def _refresh_weights16():
     global _W16_TABLE, _W16_REFRESHED
     import numpy as np
     live = []
-    for key, ent in list(_W16.items()):
-        owner = ent[0]()
-        if owner is None or not _owns(owner, key[0]):
+    for key, c in list(_W16.items()):
+        owner = c.owners[0]()           # held until its version is read below
+        if _copies_state(c, key[:1]) == "dead":
             del _W16[key]
             continue
-        live.append((key, owner, ent))
+        live.append((key, owner, c))
     _W16_REFRESHED = _W16_EPOCH
     if not live:
         return
     # the table is reused only while every entry still converts the same storage into the SAME output buffers: an entry re-created
     # under an unchanged key (a later model whose flat parameter buffer landed on the address of a freed one) has new buffers
-    sig = tuple((k, e[3].data_ptr(), e[4].data_ptr(), e[5].data_ptr() if e[5] is not None else 0, e[5].dtype if e[5] is not None else None)
-                for k, _, e in live)
-    if _W16_TABLE is None or _W16_TABLE[0] != sig:
+    second = lambda c: c.second.data_ptr() if c.second is not None else 0
+    sig = tuple((k, c.w16.data_ptr(), c.w16T.data_ptr(), second(c), c.kind) for k, _, c in live)
+    if _W16_TABLE is None or _W16_TABLE.sig != sig:
         rec = np.zeros(len(live), dtype=np.dtype([("x", "<u8"), ("out", "<u8"), ("outT", "<u8"), ("ldt", "<i8"), ("R", "<i4"),
                                                    ("C", "<i4"), ("tile0", "<i4"), ("tiles_c", "<i4"), ("out_lo", "<u8"), ("flags", "<i8")]))
         t0 = 0
-        for i, ((ptr, R, C), _, e) in enumerate(live):
-            tc = (C + 63) // 64
-            rec[i] = (ptr, e[3].data_ptr(), e[4].data_ptr(), e[4].shape[1], R, C, t0, tc, e[5].data_ptr() if e[5] is not None else 0,
-                      1 if (e[5] is not None and e[5].dtype == torch.float16) else 0)          # (an fp16 second copy: weight16(..., f16=True))
-            t0 += tc * ((max(R, e[4].shape[1]) + 63) // 64)
-        table = host_table(rec.view(np.uint8), live[0][2][3].device)
-        _W16_TABLE = (sig, table, len(live), t0)
-    _, table, n, tiles = _W16_TABLE
-    _call("spe_cvt_bf16_multi", _p(table), n, tiles, _st())
-    for key, owner, e in live:
-        _W16[key] = (e[0], owner._version, _W16_EPOCH, e[3], e[4], e[5])
+        for i, ((ptr, R, C), _, c) in enumerate(live):
+            tc, ldt = (C + 63) // 64, c.w16T.shape[1]
+            rec[i] = (ptr, c.w16.data_ptr(), c.w16T.data_ptr(), ldt, R, C, t0, tc, second(c), int(c.kind == KIND_F16))   # flag bit 0: out_lo receives fp16(x)
+            t0 += tc * ((max(R, ldt) + 63) // 64)
+        _W16_TABLE = RefreshTable(sig, host_table(rec.view(np.uint8), live[0][2].w16.device), len(live), t0)
+    _call("spe_cvt_bf16_multi", _p(_W16_TABLE.table), _W16_TABLE.njobs, _W16_TABLE.tiles, _st())
+    for _, owner, c in live:
+        c.versions, c.epoch = (owner._version,), _W16_EPOCH
 
 
 def _owns(owner, ptr):
     """The storage `owner` holds now still covers the address a cache entry was made for."""
     base = owner.data_ptr()
     return base <= ptr < base + max(1, owner.numel()) * owner.element_size()
+
+
+def _copies_state(c, ptrs, shape=None, kind=None, bias_versions=()):
+    """THE currency rule of the cached weight copies: "current" when the WeightCopies `c` may be returned as it is for the weights at the
+    addresses `ptrs`, else the first reason why not - "dead": an owner is gone or its storage no longer covers the address (the key may
+    belong to another tensor now); "epoch": weights_changed() was called since; "version": an owner's or a bias's version counter moved;
+    "kind": a second copy of `kind` is wanted and c.second is none; "shape".  Touches no device.  The batched refresh asks only for "dead"."""
+    versions = []
+    for ref, ptr in zip(c.owners, ptrs):
+        owner = ref()
+        if owner is None or not _owns(owner, ptr):
+            return "dead"
+        versions.append(owner._version)
+    if c.epoch != _W16_EPOCH:
+        return "epoch"
+    if c.versions != (*versions, *bias_versions):
+        return "version"
+    if kind is not None and c.kind != kind:
+        return "kind"
+    return "current" if c.shape == shape else "shape"
 
 
 def host_table(bytes_np, device):
@@ -469,37 +519,52 @@ def host_table(bytes_np, device):
 
 
 def weight16(W, lo=False, f16=False):
-    """(W16 [N,K], W16T [K,N]) of a contiguous 2-D weight (or 2-D view of one: the patch-embedding filter), cached until
-    the optimizer (or a state-dict load) changes it; lo=True: (W16, W16T, W16lo [N,K]) with W16lo = bf16(W - W16), the low
-    part of the split forward operand (precision mode bf16s) - or, f16=True, the IEEE fp16 copy of W (the operand of the
-    single-term fp16 forward products of the backbone MLP; such a weight never needs its low part).  Cache key: (address, shape);
-    an entry lives as long as the tensor that owns the storage.  The first lookup after weights_changed() refreshes every cached
-    copy in one launch."""
-    import weakref
-    key = (W.data_ptr(), W.shape[0], W.shape[1])
-    ent = _W16.get(key)
-    if ent is not None:
-        owner = ent[0]()
-        if owner is not None and _owns(owner, key[0]):
-            if ent[2] != _W16_EPOCH and _W16_REFRESHED != _W16_EPOCH:
-                _refresh_weights16()
-                ent = _W16.get(key, ent)
-            if ent[1] == owner._version and ent[2] == _W16_EPOCH and (not lo or (ent[5] is not None and (ent[5].dtype == torch.float16) == f16)):
-                return (ent[3], ent[4], ent[5]) if lo else (ent[3], ent[4])
-            if not lo and ent[5] is not None and ent[5].dtype == torch.float16:
-                f16 = True          # a stale entry of an fp16-forward weight looked up by its backward: it stays one
-    owner = W._base if W._base is not None else W
+    """The WeightCopies of a contiguous 2-D weight (or 2-D view of one: the patch-embedding filter): .w16 [N,K] and .w16T [K,N], cached
+    until the optimizer (or a state-dict load) changes it; lo=True: .second [N,K] is bf16(W - w16), the low part of the split forward
+    operand (precision mode bf16s) - or, f16=True, the IEEE fp16 copy of W (the operand of the single-term fp16 forward products of the
+    backbone MLP; such a weight never needs its low part).  lo=False promises nothing about .second: whether a forward uses it is the
+    caller's decision (split_fwd()).  Cache key: (address, shape); an entry lives as long as the tensor that owns the storage.  The
+    first lookup after weights_changed() refreshes every cached copy in one launch."""
+    shape = tuple(W.shape)
+    key = (W.data_ptr(), *shape)
+    kind = (KIND_F16 if f16 else KIND_LO) if lo else None
+    c = _W16.get(key)
+    if c is not None:
+        state = _copies_state(c, key[:1], shape, kind)
+        if state == "epoch" and _W16_REFRESHED != _W16_EPOCH:
+            _refresh_weights16()            # converts into the records' buffers and makes them current
+            state = _copies_state(c, key[:1], shape, kind)
+        if state == "current":
+            return c
+        if state != "dead" and not lo and c.kind == KIND_F16:
+            f16 = True          # a stale entry of an fp16-forward weight looked up by its backward: it stays one
     want_lo = lo or f16 or _PRECISION == 2
     with torch.no_grad():
         W16lo = torch.empty(W.shape, device=W.device, dtype=torch.float16 if f16 else torch.bfloat16) if want_lo else None
         W16, W16T = cvt_bf16(W.detach(), True, True, ldt=W.shape[0], out_lo=W16lo, lo_f16=f16)
     if len(_W16) > 4096:
         _W16.clear()
-    _W16[key] = (weakref.ref(owner), owner._version, _W16_EPOCH, W16, W16T, W16lo)
-    return (W16, W16T, W16lo) if lo else (W16, W16T)
+    c = _W16[key] = WeightCopies((W,), W16, W16T, W16lo)
+    return c
 
 
-_WCAT = {}      # ((address, shape) per weight) -> (owner weakrefs, epoch, versions, Wcat16, Wcat16T, bcat, Wcat16lo)
+_WCAT = {False: {}, True: {}}      # the bf16 stacks and (True) the fp16 stacks: ((address, shape) per weight) -> WeightCopies with .bias
+
+
+def _weightcat(Ws, bs, kind, build):
+    """The cached stack of the weights Ws (+ their stacked biases), else what build() -> (w16, w16T, second) makes of them now."""
+    cache = _WCAT[kind == KIND_F16]
+    key = tuple((W.data_ptr(), tuple(W.shape)) for W in Ws)
+    bvers = tuple(b._version for b in bs)
+    c = cache.get(key)
+    if c is not None and _copies_state(c, [k[0] for k in key], (sum(W.shape[0] for W in Ws), Ws[0].shape[1]), kind, bvers) == "current":
+        return c
+    with torch.no_grad():
+        c = WeightCopies(Ws, *build(), bias=torch.cat([b.detach() for b in bs]), bias_versions=bvers)
+    if len(cache) > 64:
+        cache.clear()
+    cache[key] = c
+    return c
 
 
 def weightcat16(Ws, bs, lo=False):
@@ -508,24 +573,10 @@ def weightcat16(Ws, bs, lo=False):
     lo=True: also the stacked low parts (split forward operand).  Rebuilt from the cached per-weight copies when any weight
     changed (three concatenations).  Keyed like weight16 on (address, shape) with weak references to the owning tensors: an
     `id()` can be reused by a later model in the same process."""
-    import weakref
-    key = tuple((W.data_ptr(), tuple(W.shape)) for W in Ws)
-    vers = tuple(W._version for W in Ws) + tuple(b._version for b in bs)
-    ent = _WCAT.get(key)
-    if ent is not None and ent[1] == _W16_EPOCH and ent[2] == vers and (ent[6] is not None or not lo):
-        owners = [r() for r in ent[0]]
-        if all(o is not None and _owns(o, W.data_ptr()) for o, W in zip(owners, Ws)) and ent[3].shape == (sum(W.shape[0] for W in Ws), Ws[0].shape[1]):
-            return (ent[3], ent[4], ent[5], ent[6]) if lo else (ent[3], ent[4], ent[5])
-    with torch.no_grad():
-        trip = [weight16(W, lo=lo) for W in Ws]
-        Wc = torch.cat([t_[0] for t_ in trip], 0)
-        WcT = torch.cat([t_[1] for t_ in trip], 1)
-        Wclo = torch.cat([t_[2] for t_ in trip], 0) if lo else None
-        bc = torch.cat([b.detach() for b in bs])
-    if len(_WCAT) > 64:
-        _WCAT.clear()
-    _WCAT[key] = ([weakref.ref(W._base if W._base is not None else W) for W in Ws], _W16_EPOCH, vers, Wc, WcT, bc, Wclo)
-    return (Wc, WcT, bc, Wclo) if lo else (Wc, WcT, bc)
+    def build():
+        cs = [weight16(W, lo=lo) for W in Ws]
+        return (torch.cat([c.w16 for c in cs], 0), torch.cat([c.w16T for c in cs], 1), torch.cat([c.second for c in cs], 0) if lo else None)
+    return _weightcat(Ws, bs, KIND_LO if lo else None, build)
 
 
 def gemm_splitk_into(A, B, out, M, N, K, lda, ldb, ldc, transA, transB, batch0, batch1, sA, sB, sC, alpha=1.0):
@@ -562,28 +613,11 @@ def cvt_f16(x2, out=None):
     return out
 
 
-_WCATH = {}     # fp16 stacks of weights sharing an input: key -> (owner weakrefs, epoch, versions, Wcat fp16 [n*N, K], bcat fp32)
-
-
 def weightcat_f16(Ws, bs):
-    """IEEE fp16 copy of several [N, K] weights stacked along the output axis + the stacked fp32 biases: the single-term fp16 operand
-    of the decoder's memory-side projection GEMM (spe_gemm_bf16nt, act bit 8).  Rebuilt when a weight changed (one concatenation +
-    one conversion launch)."""
-    import weakref
-    key = tuple((W.data_ptr(), tuple(W.shape)) for W in Ws)
-    vers = tuple(W._version for W in Ws) + tuple(b._version for b in bs)
-    ent = _WCATH.get(key)
-    if ent is not None and ent[1] == _W16_EPOCH and ent[2] == vers:
-        owners = [r() for r in ent[0]]
-        if all(o is not None and _owns(o, W.data_ptr()) for o, W in zip(owners, Ws)):
-            return ent[3], ent[4]
-    with torch.no_grad():
-        Wh = cvt_f16(torch.cat([W.detach() for W in Ws], 0))
-        bc = torch.cat([b.detach() for b in bs])
-    if len(_WCATH) > 64:
-        _WCATH.clear()
-    _WCATH[key] = ([weakref.ref(W._base if W._base is not None else W) for W in Ws], _W16_EPOCH, vers, Wh, bc)
-    return Wh, bc
+    """IEEE fp16 copy (.second, nothing else) of several [N, K] weights stacked along the output axis + the stacked fp32 biases: the
+    single-term fp16 operand of the decoder's memory-side projection GEMM (spe_gemm_bf16nt, act bit 8).  Rebuilt when a weight changed
+    (one concatenation + one conversion launch)."""
+    return _weightcat(Ws, bs, KIND_F16, lambda: (None, None, cvt_f16(torch.cat([W.detach() for W in Ws], 0))))
 
 
 def kv_frags(ym16, yp16, L, B, S, H, dh, train):
@@ -690,8 +724,8 @@ def linear_res_fwd(x2, W, b, res, gamma, save=True, src=None, drop=None, sscale=
     out = torch.empty((R, N), device=dev, dtype=torch.float32)
     # the branch output y is kept for the LayerScale gamma gradient only (dgamma = sum dout * y): fp16, like the MLP's pre-activation
     y = torch.empty((R, N), device=dev, dtype=torch.float16 if MLP_PRE_F16 else torch.float32) if save else None
-    Wt = weight16(W, lo=sp)
-    gemm16_ex(x16, Wt[0], R, N, K, K, K, bias=b, C=out, C2=y, res=res, rgamma=gamma, Alo=x16lo, Blo=Wt[2] if sp else None,
+    Wc = weight16(W, lo=sp)
+    gemm16_ex(x16, Wc.w16, R, N, K, K, K, bias=b, C=out, C2=y, res=res, rgamma=gamma, Alo=x16lo, Blo=Wc.second if sp else None,
               drop=drop, sscale=sscale, rps=rps)
     return out, (x16, y)
 
@@ -712,7 +746,7 @@ def linear_res_bwd(dout2, saved, W, gamma, need_dx=True, grad_bufs=(None, None, 
     dx = None
     if need_dx:
         dx = torch.empty((R, K), device=dout2.device, dtype=torch.float32)
-        gemm16(dy16, weight16(W)[1], dx, R, K, N, N, N, K)
+        gemm16(dy16, weight16(W).w16T, dx, R, K, N, N, N, K)
     return dx, dW, db, dg
 
 
@@ -767,7 +801,7 @@ def mlp_gelu_fwd(x2, W1, b1, W2, b2, res=None, gamma=None, save=True, src=None, 
         pre = torch.empty((R, Hd), device=dev, dtype=torch.float16 if MLP_PRE_F16 else torch.float32) if save else None
         h16 = torch.empty((R, Hd), device=dev, dtype=torch.bfloat16)
         hh = torch.empty((R, Hd), device=dev, dtype=torch.float16)
-        W1h, W2h = weight16(W1, lo=True, f16=True)[2], weight16(W2, lo=True, f16=True)[2]
+        W1h, W2h = weight16(W1, lo=True, f16=True).second, weight16(W2, lo=True, f16=True).second
         gemm16_ex(xh, W1h, R, Hd, K, K, K, bias=b1, C2=pre, out16=h16, act=2, out16lo=hh, drop=drop1, op_f16=True)
         out = torch.empty((R, N), device=dev, dtype=torch.float32)
         y = torch.empty((R, N), device=dev, dtype=torch.float16 if MLP_PRE_F16 else torch.float32) if save else None
@@ -779,19 +813,19 @@ def mlp_gelu_fwd(x2, W1, b1, W2, b2, res=None, gamma=None, save=True, src=None, 
     pre = torch.empty((R, Hd), device=dev, dtype=torch.float16 if MLP_PRE_F16 else torch.float32) if save else None
     h16 = torch.empty((R, Hd), device=dev, dtype=torch.bfloat16)
     h16lo = torch.empty((R, Hd), device=dev, dtype=torch.bfloat16) if sp else None
-    W1t, W2t = weight16(W1, lo=sp), weight16(W2, lo=sp)
-    W1lo, W2lo = (W1t[2], W2t[2]) if sp else (None, None)
+    W1c, W2c = weight16(W1, lo=sp), weight16(W2, lo=sp)
+    W1lo, W2lo = (W1c.second, W2c.second) if sp else (None, None)
     # drop1 = (p, seed, offset): timm Mlp's dropout after the activation - h16 then holds dropout(gelu(pre))
-    gemm16_ex(x16, W1t[0], R, Hd, K, K, K, bias=b1, C2=pre, out16=h16, act=2, Alo=x16lo, Blo=W1lo, out16lo=h16lo, drop=drop1)
+    gemm16_ex(x16, W1c.w16, R, Hd, K, K, K, bias=b1, C2=pre, out16=h16, act=2, Alo=x16lo, Blo=W1lo, out16lo=h16lo, drop=drop1)
     y = torch.empty((R, N), device=dev, dtype=torch.float32)
     if res is None:
-        gemm16(h16, W2t[0], y, R, N, Hd, Hd, Hd, N, bias=b2, Alo=h16lo, Blo=W2lo)
+        gemm16(h16, W2c.w16, y, R, N, Hd, Hd, Hd, N, bias=b2, Alo=h16lo, Blo=W2lo)
         return y, (x16, pre, h16)
     # LayerScale residual in the fc2 epilogue: out = res + gamma * y ; y is kept for the gamma gradient
     out = torch.empty((R, N), device=dev, dtype=torch.float32)
     if MLP_PRE_F16:
         y = torch.empty((R, N), device=dev, dtype=torch.float16)        # kept for the gamma gradient only
-    gemm16_ex(h16, W2t[0], R, N, Hd, Hd, Hd, bias=b2, C=out, C2=y if save else None, res=res, rgamma=gamma, Alo=h16lo, Blo=W2lo,
+    gemm16_ex(h16, W2c.w16, R, N, Hd, Hd, Hd, bias=b2, C=out, C2=y if save else None, res=res, rgamma=gamma, Alo=h16lo, Blo=W2lo,
               drop=drop2, sscale=sscale, rps=rps)
     return out, (x16, pre, h16, y)
 
@@ -842,12 +876,12 @@ def mlp_gelu_bwd(dy2, saved, W1, W2, need_dx=True, grad_bufs=(None, None, None, 
     # dpre = (dy @ W2) * gelu'(pre): bf16 only
     db1 = _zeros_or(gb1, Hd, dev)
     dp16 = torch.empty((R, Hd), device=dev, dtype=torch.bfloat16)
-    gemm16_ex(dy16, weight16(W2)[1], R, Hd, N, N, N, out16=dp16, colsum=db1, aux=pre, act=2, drop=drop1)      # ... times the mask of drop1
+    gemm16_ex(dy16, weight16(W2).w16T, R, Hd, N, N, N, out16=dp16, colsum=db1, aux=pre, act=2, drop=drop1)      # ... times the mask of drop1
     dW1 = _dw16_tn(dp16, x16, Hd, K, R, gW1)
     dx = None
     if need_dx:
         dx = torch.empty((R, K), device=dev, dtype=torch.float32)
-        gemm16(dp16, weight16(W1)[1], dx, R, K, Hd, Hd, Hd, K)
+        gemm16(dp16, weight16(W1).w16T, dx, R, K, Hd, Hd, Hd, K)
     if gamma is not None:
         return dx, dW1, db1, dW2, db2, dg
     return dx, dW1, db1, dW2, db2
@@ -855,21 +889,39 @@ def mlp_gelu_bwd(dy2, saved, W1, W2, need_dx=True, grad_bufs=(None, None, None, 
 
 def act16(x2, src=None, want_lo=False, lo_f16=False):
     """Row-major bf16 copy (and the low part of the split operand when want_lo) of an activation [R,K] -> (x16, x16lo).
-    `src`: the tensor object the caller holds (x2 is a reshape of it) - the copies are remembered ON that object (attribute
-    _spe16 = (version, x16, None, x16lo): see attach16; checked against its version counter), so an activation that feeds several
-    Linears (the decoder's memory, positional embedding, tgt, query_pos; q / k / v of the class attention) is converted once; they
-    die with the tensor."""
-    if src is not None:
-        ent = getattr(src, "_spe16", None)
-        if (ent is not None and ent[0] == src._version and ent[1].shape == x2.shape
-                and (not want_lo or (ent[3] is not None and (ent[3].dtype == torch.float16) == lo_f16))):
-            return ent[1], (ent[3] if want_lo else None)
+    `src`: the tensor object the caller holds (x2 is a reshape of it) - the copies are remembered ON that object (an ActCopies
+    record: see attach16; checked against its version counter), so an activation that feeds several Linears (the decoder's memory,
+    positional embedding, tgt, query_pos; q / k / v of the class attention) is converted once; they die with the tensor."""
+    x16, x16lo = cached16(x2, src, (KIND_F16 if lo_f16 else KIND_LO) if want_lo else None)
+    if x16 is not None:
+        return x16, x16lo
     # lo_f16: the second copy is IEEE fp16(x) - the operand of a single-term fp16 product - instead of the low part of the split
     x16lo = torch.empty(x2.shape, device=x2.device, dtype=torch.float16 if lo_f16 else torch.bfloat16) if want_lo else None
     x16, _ = cvt_bf16(x2, True, False, out_lo=x16lo, lo_f16=lo_f16 and want_lo)
     if src is not None:
         attach16(src, x16, x16lo)
     return x16, x16lo
+
+
+def cached16(x2, src, kind=None):
+    """(x16, second): the current bf16 copy of x2 remembered on `src` and, when `kind` asks for one, its second copy of that kind - or
+    (None, None): nothing attached, `src` written since, another shape, or another kind of second copy.  Touches no device."""
+    c = getattr(src, "_spe16", None) if src is not None else None
+    if c is None or c.version != src._version or c.x16.shape != x2.shape or (kind is not None and c.kind != kind):
+        return None, None
+    return c.x16, (c.second if kind is not None else None)
+
+
+def _x16_small(x2, src, want=True):
+    """bf16(x2) for a small-row Linear launch -> (x16, x16_out): the copy `src` carries, else (if wanted) a fresh buffer the launch fills
+    as x16_out, attached to `src`."""
+    x16, _ = cached16(x2, src)
+    if x16 is not None or not want:
+        return x16, None
+    x16 = torch.empty(x2.shape, device=x2.device, dtype=torch.bfloat16)
+    if src is not None:
+        attach16(src, x16)
+    return x16, x16
 
 
 def linear_fwd(x2, W, b, act=0, want_pre=False, save_for_dw=True, src=None):
@@ -884,22 +936,16 @@ def linear_fwd(x2, W, b, act=0, want_pre=False, save_for_dw=True, src=None):
         # a few hundred rows (decoder / heads): one launch straight from the fp32 activations (csrc/linear_small.hip); it also
         # leaves bf16(x) behind for the backward unless the activation already carries one
         sp = split_fwd()
-        Wt = weight16(W, lo=sp)
-        ent = getattr(src, "_spe16", None) if src is not None else None
-        x16 = ent[1] if (ent is not None and ent[0] == src._version and ent[1].shape == x2.shape) else None
-        x16_out = None
-        if x16 is None and save_for_dw:
-            x16 = x16_out = torch.empty((R, K), device=x2.device, dtype=torch.bfloat16)
-            if src is not None:
-                attach16(src, x16)
-        _call("spe_linear_small_fwd", _p(x2), x2.stride(0), _p(Wt[0]), _p(Wt[2] if sp else None), _p(b), _p(y), _p(pre), _p(x16_out),
+        Wc = weight16(W, lo=sp)
+        x16, x16_out = _x16_small(x2, src, save_for_dw)
+        _call("spe_linear_small_fwd", _p(x2), x2.stride(0), _p(Wc.w16), _p(Wc.second if sp else None), _p(b), _p(y), _p(pre), _p(x16_out),
               R, N, K, N, int(act), _st())
         return y, pre, (x16 if save_for_dw else x2)
     if _lin16_ok(R, N, K) and W.is_contiguous():
         sp = split_fwd()
         x16, x16lo = act16(x2, src, want_lo=sp)
-        Wt = weight16(W, lo=sp)
-        gemm16(x16, Wt[0], y, R, N, K, K, K, N, bias=b, C2=pre, act=act, Alo=x16lo, Blo=Wt[2] if sp else None)
+        Wc = weight16(W, lo=sp)
+        gemm16(x16, Wc.w16, y, R, N, K, K, K, N, bias=b, C2=pre, act=act, Alo=x16lo, Blo=Wc.second if sp else None)
         return y, pre, (x16 if save_for_dw else x2)
     gemm(x2, W, y, R, N, K, K, K, N, False, True, bias=b, C2=pre, act=act)
     return y, pre, x2
@@ -923,17 +969,11 @@ def linear_group_fwd(x2, Ws, bs, src=None, adds=None):
     R, K = x2.shape
     N = Ws[0].shape[0]
     sp = split_fwd()
-    trip = [weight16(W, lo=sp) for W in Ws]
-    ent = getattr(src, "_spe16", None) if src is not None else None
-    x16 = ent[1] if (ent is not None and ent[0] == src._version and ent[1].shape == x2.shape) else None
-    x16_out = None
-    if x16 is None:
-        x16 = x16_out = torch.empty((R, K), device=x2.device, dtype=torch.bfloat16)
-        if src is not None:
-            attach16(src, x16)
+    cs = [weight16(W, lo=sp) for W in Ws]
+    x16, x16_out = _x16_small(x2, src)
     ys = [torch.empty((R, N), device=x2.device, dtype=torch.float32) for _ in Ws]
-    _call("spe_linear_small_group_fwd", _p(x2), x2.stride(0), _ptr_array([t_[0].data_ptr() for t_ in trip]),
-          _ptr_array([t_[2].data_ptr() for t_ in trip]) if sp else None, _ptr_array([b.data_ptr() for b in bs]),
+    _call("spe_linear_small_group_fwd", _p(x2), x2.stride(0), _ptr_array([c.w16.data_ptr() for c in cs]),
+          _ptr_array([c.second.data_ptr() for c in cs]) if sp else None, _ptr_array([b.data_ptr() for b in bs]),
           _ptr_array([0 if a is None else a.data_ptr() for a in adds]) if adds is not None else None,
           _ptr_array([y.data_ptr() for y in ys]), _p(x16_out), R, len(Ws), N, K, _st())
     return ys, x16
@@ -955,7 +995,7 @@ def linear_group_bwd(dys, x16, Ws, need_dx, dW_outs, db_outs):
         dWs.append(dW_outs[i] if dW_outs[i] is not None else torch.empty((N, K), device=dev, dtype=torch.float32))
         dbs.append(db_outs[i].view(-1) if db_outs[i] is not None else torch.empty((N,), device=dev, dtype=torch.float32))
     _call("spe_linear_small_group_bwd", _ptr_array([0 if d is None else d.data_ptr() for d in dys]), _p(x16),
-          _ptr_array([weight16(W)[1].data_ptr() for W in Ws]) if need_dx else None, _p(dx),
+          _ptr_array([weight16(W).w16T.data_ptr() for W in Ws]) if need_dx else None, _p(dx),
           _ptr_array([0 if w is None else w.data_ptr() for w in dWs]), _ptr_array([0 if b is None else b.data_ptr() for b in dbs]),
           R, n, N, K, _st())
     return dx, dWs, dbs
@@ -980,7 +1020,7 @@ def linear_bwd(dy2, xsave, W, need_dx=True, need_dw=True, need_db=True, dW_out=N
         if need_db:
             db = db_out.view(-1) if db_out is not None else torch.empty((N,), device=dev, dtype=torch.float32)
         _call("spe_linear_small_bwd", _p(dy2), _p(act_aux if act else None), int(act), _p(xsave if need_dw else None),
-              _p(weight16(W)[1] if need_dx else None), _p(dx), _p(dW), _p(db), R, N, K, _st())
+              _p(weight16(W).w16T if need_dx else None), _p(dx), _p(dW), _p(db), R, N, K, _st())
         return dx, dW, db
     if (x16 or not need_dw) and _lin16_ok(R, N, K) and W.is_contiguous():
         if need_db:                     # the bias gradient rides on the conversion pass over dy
@@ -989,7 +1029,7 @@ def linear_bwd(dy2, xsave, W, need_dx=True, need_dw=True, need_db=True, dW_out=N
         need_db = False
         if need_dx:
             dx = torch.empty((R, K), device=dy2.device, dtype=torch.float32)
-            gemm16(dy16, weight16(W)[1], dx, R, K, N, N, N, K)
+            gemm16(dy16, weight16(W).w16T, dx, R, K, N, N, N, K)
         if need_dw:                     # (only with a bf16 save: see the test above)
             dW = _dw16_tn(dy16, xsave, N, K, R, dW_out)
     else:
@@ -1053,8 +1093,9 @@ def produces16(R, C):
 
 
 def attach16(t, x16, x16lo=None):
-    """Remember the bf16 copy (and the low part of the split operand) ON the activation tensor (what act16 looks up)."""
-    t._spe16 = (t._version, x16, None, x16lo)
+    """Remember the bf16 copy (and the low part of the split operand, or the fp16 copy in its place) ON the activation tensor (what
+    cached16 looks up): the only writer of the attribute."""
+    t._spe16 = ActCopies(t, x16, x16lo)
 
 
 LN_LS_FUSE = True        # LayerScale backward of the consuming node inside the LayerNorm backward (module attribute: the tests run both settings)

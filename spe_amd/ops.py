@@ -77,12 +77,11 @@ class _MultiLinear(Function):
         N = Ws[0].shape[0]
         sp = K.split_fwd()                    # bf16s forward: (hi, lo) operand pairs
         cat = K.weightcat16(Ws, bs, lo=sp)
-        Wc, WcT, bc = cat[:3]
         x16, x16lo = K.act16(x2, x, want_lo=sp)
         y = torch.empty((R, n * N), device=x.device, dtype=torch.float32)
-        K.gemm16(x16, Wc, y, R, n * N, Kd, Kd, Kd, n * N, bias=bc, Alo=x16lo, Blo=cat[3] if sp else None)
+        K.gemm16(x16, cat.w16, y, R, n * N, Kd, Kd, Kd, n * N, bias=cat.bias, Alo=x16lo, Blo=cat.second if sp else None)
         ctx.params = (Ws, bs)
-        ctx.save_for_backward(x16, WcT)
+        ctx.save_for_backward(x16, cat.w16T)
         ctx.dims = (n, N, Kd, R)
         y = y.view(*shp[:-1], n * N)
         return tuple(y[..., i * N:(i + 1) * N] for i in range(n))
@@ -604,7 +603,7 @@ class _QkvTalkingAttention(Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty((R, Kd), device=dev, dtype=torch.float32)
-            K.gemm16(d16, K.weight16(Wq)[1], dx, R, Kd, N3, N3, N3, Kd)
+            K.gemm16(d16, K.weight16(Wq).w16T, dx, R, Kd, N3, N3, N3, Kd)
             dx = dx.view(*dO.shape[:-1], Kd)
         return dx, dW, db.view_as(bq), dWl, dbl, dWw, dbw, None, None, None, None
 
@@ -1008,12 +1007,12 @@ class _MemorySideKV(Function):
         # can: needs_input_grad still reports the parameters' requires_grad there, so it must not decide alone
         grad_mode = bool(getattr(holder, "want_bwd", True))
         train = grad_mode
-        Wmh, bmc = K.weightcat_f16(Wm, bm)
-        Wph, bpc = K.weightcat_f16(Wp, bp)
+        Wmh = K.weightcat_f16(Wm, bm)
+        Wph = K.weightcat_f16(Wp, bp)
         ym = torch.empty((B * S, 2 * L * d), device=memory.device, dtype=torch.float16)
         yp = torch.empty((B * S, L * d), device=memory.device, dtype=torch.float16)
-        K.gemm16(K.cvt_f16(m2), Wmh, ym, B * S, 2 * L * d, d, d, d, 2 * L * d, bias=bmc, act=0x300)
-        K.gemm16(K.cvt_f16(p2), Wph, yp, B * S, L * d, d, d, d, L * d, bias=bpc, act=0x300)
+        K.gemm16(K.cvt_f16(m2), Wmh.second, ym, B * S, 2 * L * d, d, d, d, 2 * L * d, bias=Wmh.bias, act=0x300)
+        K.gemm16(K.cvt_f16(p2), Wph.second, yp, B * S, L * d, d, d, d, L * d, bias=Wph.bias, act=0x300)
         holder.Kf, holder.V16, holder.K16, holder.Vf = K.kv_frags(ym, yp, L, B, S, H, dh, train)
         holder.dims = (L, B, S, H, dh)
         holder.ztok = torch.zeros((1,), device=memory.device, dtype=torch.float32)
@@ -1024,7 +1023,7 @@ class _MemorySideKV(Function):
             # other consumers of `memory` / `pos`) and the transposed bf16 weight stack for the input gradient
             m16, _ = K.act16(m2, memory)
             p16, _ = K.act16(p2, pos)
-            ctx.save_for_backward(m16, p16, K.weightcat16(Wm, bm)[1])
+            ctx.save_for_backward(m16, p16, K.weightcat16(Wm, bm).w16T)
         toks = tuple(torch.zeros((1,), device=memory.device, dtype=torch.float32) for _ in range(L))
         return toks
 
@@ -1061,7 +1060,7 @@ class _MemorySideKV(Function):
         dpos = None
         if ctx.needs_input_grad[2]:
             dpos = torch.empty((R, d), device=dev, dtype=torch.float32)
-            K.gemm16(h.dYp, K.weightcat16(Wp, bp)[1], dpos, R, d, L * d, L * d, L * d, d)
+            K.gemm16(h.dYp, K.weightcat16(Wp, bp).w16T, dpos, R, d, L * d, L * d, L * d, d)
             dpos = dpos.view(B, S, d)
         h.dYm = h.dYp = None
         h.written = set()

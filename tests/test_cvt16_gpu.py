@@ -503,16 +503,45 @@ def test_cached_copies_and_batched_refresh(dev):
         Ws = [h.to(dev) for h in hosts]
         f16 = [False, True, False, True, False, True]
         for W, h, f in zip(Ws, hosts, f16):
-            W16, W16T, lo = K.weight16(W, lo=True, f16=f)
-            _check_weight(h, W16, W16T, lo, f, "weight16 %s" % (tuple(h.shape),))
-            assert K.weight16(W, lo=True, f16=f)[2] is lo                         # cached
+            c = K.weight16(W, lo=True, f16=f)
+            assert c.kind == (K.KIND_F16 if f else K.KIND_LO)
+            _check_weight(h, c.w16, c.w16T, c.second, f, "weight16 %s" % (tuple(h.shape),))
+            assert K.weight16(W, lo=True, f16=f).second is c.second                 # cached
         # activations
         xh = _data(67, 40, 400, "MAIN_BITS")
         xd = xh.to(dev)
+
+        def check_act(x16, x16lo, lf, tag):
+            _assert_bits(_i16(x16), CR.bf16_rne_bits(xh), "bf16", tag + " x16")
+            _assert_bits(_i16(x16lo), CR.f16_sat_bits(xh) if lf else CR.lo_bits(xh), "f16" if lf else "bf16", tag + " x16lo")
         for lf in (False, True):
-            x16, x16lo = K.act16(xd, want_lo=True, lo_f16=lf)
-            _assert_bits(_i16(x16), CR.bf16_rne_bits(xh), "bf16", "act16 x16")
-            _assert_bits(_i16(x16lo), CR.f16_sat_bits(xh) if lf else CR.lo_bits(xh), "f16" if lf else "bf16", "act16 x16lo")
+            check_act(*K.act16(xd, want_lo=True, lo_f16=lf), lf, "act16")
+        # ... remembered on the tensor the caller holds: the same tensors again, re-made after a write, and when the other kind of second
+        # copy is asked for (low part -> fp16 -> low part)
+        src = xd.clone()
+        x16, x16lo = K.act16(src.view(67, 40), src, want_lo=True)
+        again = K.act16(src.view(67, 40), src, want_lo=True)
+        assert again[0] is x16 and again[1] is x16lo
+        assert K.act16(src.view(67, 40), src)[0] is x16                                   # no second copy asked for: any kind serves
+        src.add_(1)
+        xh = src.cpu()                                                                    # what the copies are now made of
+        y16, y16lo = K.act16(src.view(67, 40), src, want_lo=True)
+        assert y16 is not x16 and y16lo is not x16lo
+        check_act(y16, y16lo, False, "act16 after add_")
+        for lf in (True, False):
+            z16, z16lo = K.act16(src.view(67, 40), src, want_lo=True, lo_f16=lf)
+            assert z16 is not y16 and z16lo is not y16lo and src._spe16.kind == (K.KIND_F16 if lf else K.KIND_LO)
+            check_act(z16, z16lo, lf, "act16 other kind")
+            y16, y16lo = z16, z16lo
+        # a weight cached without a low part (precision bf16) gets one when a lookup asks for it
+        K.set_precision("bf16")
+        Wn = hosts[0].to(dev)
+        c = K.weight16(Wn)
+        assert c.second is None and c.kind is None and K.weight16(Wn) is c
+        K.set_precision("bf16s")
+        c2 = K.weight16(Wn, lo=True)
+        assert c2 is not c and c2.kind == K.KIND_LO and K._W16[(Wn.data_ptr(), 65, 129)] is c2
+        _check_weight(hosts[0], c2.w16, c2.w16T, c2.second, False, "weight16 bf16 -> lo")
         # stacks of weights that share an input
         cat_h = [_data(R, 40, 500 + R, "MAIN_BITS") for R in (24, 65, 8)]
         cat = [h.to(dev) for h in cat_h]
@@ -520,12 +549,13 @@ def test_cached_copies_and_batched_refresh(dev):
 
         def check_cat():
             allh = torch.cat(cat_h, 0)
-            Wc, WcT, bc, Wclo = K.weightcat16(cat, bs, lo=True)
-            _check_weight(allh, Wc, WcT, Wclo, False, "weightcat16")
-            assert torch.equal(bc.cpu(), torch.cat([b.cpu() for b in bs]))
-            Wh, bc2 = K.weightcat_f16(cat, bs)
-            _assert_bits(_i16(Wh), CR.f16_sat_bits(allh), "f16", "weightcat_f16")
-            assert torch.equal(bc2.cpu(), bc.cpu())
+            c = K.weightcat16(cat, bs, lo=True)
+            _check_weight(allh, c.w16, c.w16T, c.second, False, "weightcat16")
+            assert torch.equal(c.bias.cpu(), torch.cat([b.cpu() for b in bs]))
+            ch = K.weightcat_f16(cat, bs)
+            assert ch.kind == K.KIND_F16 and ch.w16 is None and ch.w16T is None
+            _assert_bits(_i16(ch.second), CR.f16_sat_bits(allh), "f16", "weightcat_f16")
+            assert torch.equal(ch.bias.cpu(), c.bias.cpu())
         check_cat()
         # raw update: new values under unchanged version counters, then the epoch bump of a raw-pointer optimizer
         vers = [W._version for W in Ws + cat]
@@ -537,10 +567,10 @@ def test_cached_copies_and_batched_refresh(dev):
         first = K.weight16(Ws[2], lo=True)
         key = lambda W: (W.data_ptr(), W.shape[0], W.shape[1])
         for W, h, f in zip(Ws, hosts, f16):
-            ent = K._W16[key(W)]
-            assert ent[2] == K._W16_EPOCH                                           # refreshed by the one launch, not on demand
-            _check_weight(h, ent[3], ent[4], ent[5], f, "refreshed %s" % (tuple(h.shape),))
-        assert first[0] is K._W16[key(Ws[2])][3]
+            c = K._W16[key(W)]
+            assert c.epoch == K._W16_EPOCH                                          # refreshed by the one launch, not on demand
+            _check_weight(h, c.w16, c.w16T, c.second, f, "refreshed %s" % (tuple(h.shape),))
+        assert first.w16 is K._W16[key(Ws[2])].w16
         check_cat()
     finally:
         K.set_precision(prec)

@@ -1015,21 +1015,21 @@ def test_weight_copies_batched_refresh(dev):
     # all copies are current now (no further conversion launches needed) and equal the single-matrix kernel's output
     key = lambda W: (W.data_ptr(), W.shape[0], W.shape[1])
     for W in Ws:
-        ent = K._W16[key(W)]
-        assert ent[2] == K._W16_EPOCH
+        c = K._W16[key(W)]
+        assert c.epoch == K._W16_EPOCH
         W16, W16T = K.cvt_bf16(W, True, True, ldt=W.shape[0])
-        assert torch.equal(ent[3], W16) and torch.equal(ent[4], W16T), W.shape
+        assert torch.equal(c.w16, W16) and torch.equal(c.w16T, W16T), W.shape
         assert torch.equal(W16.float(), W.to(torch.bfloat16).float()) and torch.equal(W16T, W16.t())
-    assert first[0] is K._W16[key(Ws[3])][3]
-    assert K._W16_TABLE[2] == len(K._W16)                                                # the dead weight left the table
+    assert first.w16 is K._W16[key(Ws[3])].w16
+    assert K._W16_TABLE.njobs == len(K._W16)                                             # the dead weight left the table
     # a 2-D view of a 4-D filter (the patch embedding) is cached under its address: no new entry per call
     conv = torch.randn(64, 3, 4, 4, generator=g).to(dev)
-    a16 = K.weight16(conv.view(64, -1))[0]
-    assert K.weight16(conv.view(64, -1))[0] is a16
+    a16 = K.weight16(conv.view(64, -1)).w16
+    assert K.weight16(conv.view(64, -1)).w16 is a16
     # an in-place torch update of one weight (version bump, same epoch) converts just that one
     with torch.no_grad():
         Ws[0].mul_(0.5)
-    assert torch.equal(K.weight16(Ws[0])[0].float(), Ws[0].to(torch.bfloat16).float())
+    assert torch.equal(K.weight16(Ws[0]).w16.float(), Ws[0].to(torch.bfloat16).float())
 
 
 def test_patch_embed_large(dev):

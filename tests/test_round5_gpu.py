@@ -266,7 +266,7 @@ def test_batched_weight_refresh_follows_recreated_cache_entries(dev):
     W.data.mul_(1.5)                      # an update through raw pointers (what FlatAdamW does): no version bump ...
     K.weights_changed()                   # ... the epoch says so
     a = K.weight16(W, lo=True)            # batched refresh: builds the job table
-    assert torch.equal(a[0].float(), W.to(torch.bfloat16).float())
+    assert torch.equal(a.w16.float(), W.to(torch.bfloat16).float())
     del W, a
     gc.collect()
     W2 = torch.randn(shape, generator=g).to(dev)
@@ -278,9 +278,9 @@ def test_batched_weight_refresh_follows_recreated_cache_entries(dev):
     b = K.weight16(W2, lo=True)           # batched refresh again: same keys as the cached table
     torch.cuda.synchronize()
     hi = W2.to(torch.bfloat16)
-    assert torch.equal(b[0].float(), hi.float())
-    assert torch.equal(b[1].float(), hi.t().float())
-    assert torch.equal(b[2].float(), (W2 - hi.float()).to(torch.bfloat16).float())
+    assert torch.equal(b.w16.float(), hi.float())
+    assert torch.equal(b.w16T.float(), hi.t().float())
+    assert torch.equal(b.second.float(), (W2 - hi.float()).to(torch.bfloat16).float())
 
 
 def test_mlp_forward_on_fp16_operands(dev):
@@ -308,7 +308,7 @@ def test_mlp_forward_on_fp16_operands(dev):
             ok = K.mlp_f16_ok(B * N, C, Hd, C)
             assert ok == f16
             y, xs = norm.skip(x, ok)
-            assert (y._spe16[3].dtype == torch.float16) == f16          # LayerNorm emitted the fp16 copy in place of the low part
+            assert (y._spe16.second.dtype == torch.float16) == f16          # LayerNorm emitted the fp16 copy in place of the low part
             out = ops.mlp_gelu_residual(y, W1, b1, W2, b2, xs, gamma)
             gr = torch.autograd.grad(out, [x, W1, b1, W2, b2, gamma], go)
             res[f16] = (out.detach(), gr)
@@ -330,9 +330,9 @@ def test_mlp_forward_on_fp16_operands(dev):
         W1.data.mul_(1.25)
         K.weights_changed()
         w = K.weight16(W1, lo=True, f16=True)
-        assert w[2].dtype == torch.float16 and torch.equal(w[2], W1.detach().to(torch.float16)) and torch.equal(w[0], W1.detach().to(torch.bfloat16))
-        assert torch.equal(K.weight16(W1)[1], W1.detach().to(torch.bfloat16).t())        # the backward's lookup keeps the entry
-        assert K.weight16(W1, lo=True, f16=True)[2].data_ptr() == w[2].data_ptr()
+        assert w.second.dtype == torch.float16 and w.kind == K.KIND_F16 and torch.equal(w.second, W1.detach().to(torch.float16)) and torch.equal(w.w16, W1.detach().to(torch.bfloat16))
+        assert torch.equal(K.weight16(W1).w16T, W1.detach().to(torch.bfloat16).t())        # the backward's lookup keeps the entry
+        assert K.weight16(W1, lo=True, f16=True).second.data_ptr() == w.second.data_ptr()
     finally:
         K.MLP_F16 = saved
 
