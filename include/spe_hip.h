@@ -50,7 +50,8 @@ typedef struct ihipStream_t* spe_stream_t; /* == hipStream_t */
  * spe_cam_targets / spe_refine_pick (the training targets assembled on the device: CAM boxes -> target rows, the stage k+1 picks in one launch)
  * spe_pseudo_quality (the quality of the pseudo labels against the loader's ground truth: per-class counters kept on the device)
  * spe_proposal_recall (recall-at-k and ceiling of a stage's Q query boxes against the loader's ground truth: per-class counters kept on the device)
- * - 116 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
+ * spe_rowops_plan (the kernel and grid the column-sum, LayerScale, activation-backward and dropout launchers choose for a shape, host only)
+ * - 117 entry points.  Still 7: spe_mha_bwd refuses nch > 1 without dq_ws (-2) instead of adding the chunks into dq atomically (no caller did). */
 int spe_abi_version(void);
 
 /* ---- reduction workspace --------------------------------------------------------------------
@@ -477,6 +478,18 @@ int spe_layernorm_res_bwd(const float* dy, const float* dy2, const float* sum, c
 /* ---- dropout y = x*keepscale (nn.Dropout at cait.py:387,391, transformer.py:266-288, timm Mlp);
  * the backward is the same call on dy. */
 int spe_dropout(const float* x, float* y, long n, float p, uint64_t seed, uint64_t offset, spe_stream_t stream);
+
+/* spe_rowops_plan: the kernel and grid that spe_colsum (launcher 0), spe_layerscale_residual_fwd (1), spe_layerscale_residual_bwd (2),
+ * spe_layerscale_residual_bwd16 / _bwd16d (3), spe_act_bwd (4) and spe_dropout (5) choose for a shape.  Host only: no device, no stream,
+ * nothing is launched; the launchers fill their launch from the same functions, so tests and tools can tell which branch a shape takes.
+ * R, C: rows and columns (launchers 4 and 5: R = n, C ignored); ld: the leading dimension of spe_colsum's input, ldt of launcher 3, ignored
+ * elsewhere; aligned: every pointer the launcher inspects is 16-B aligned (launchers 0, 2, 3).
+ * v[4] = { kernel, grid.x, grid.y, members of the fixed-order sum across workgroups (csrc/det_reduce.h; 0: the kernel has none) };
+ * kernel: 0 nothing is launched, 1 colsum_wide_kernel, 2 colsum_tall4_kernel, 3 colsum_kernel, 4 lsres_fwd_kernel,
+ * 5 lsres_bwd_rows_kernel<16>, 6 lsres_bwd_kernel, 7 lsres_bwd16_kernel<2>, 8 lsres_bwd16_kernel<4>, 9 act_bwd_kernel, 10 dropout_kernel.
+ * Returns the status the launcher would return for the shape (the rate / rows_per_sample refusals of _bwd16d and -4 aside); -2 for an
+ * unknown launcher. */
+int spe_rowops_plan(int launcher, long R, int C, long ld, int aligned, long* v);
 
 /* ---- patch gather for the 16x16 stride-16 patch-embed conv (reference models/cait.py:518-528):
  * img[B,Cin,Hi,Wi] -> cols[B*(Hi/P)*(Wi/P), Cin*P*P] in conv-weight column order. */

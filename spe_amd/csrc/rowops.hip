@@ -500,25 +500,46 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ i
                [&](int k) { return red[0][k] + red[1][k] + red[2][k] + red[3][k]; },
                [&](int k, float s) { const int cc = blockIdx.x * 64 + k; if (cc < C) out[cc] = accumulate ? out[cc] + s : s; });
 }
-extern "C" int spe_colsum(const float* in, float* out, long R, int C, long ld, int accumulate, hipStream_t st) {
-    if (C <= 0) return 0;
-    if (R <= 0) { if (!accumulate) { hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)C, st); if (e != hipSuccess) return (int)e; } return 0; }
-    const bool al4 = (C % 4 == 0) && (ld % 4 == 0) && ((((uintptr_t)in) | ((uintptr_t)out)) % 16 == 0);
+// The grid arithmetic of the launchers of this half of the file, one host function per launcher: kernel (ROWOPS_*, 0 = nothing is
+// launched), grid and the members of the cross-workgroup sum (det_reduce.h; 0 = the kernel has none).  The launchers fill their launch
+// from these and spe_rowops_plan (include/spe_hip.h) answers from the same functions, so tests can tell which branch a shape takes.
+// aligned: what the launcher found out about its pointers (16-B aligned); status: what the launcher returns for the shape.
+enum { ROWOPS_NONE = 0, ROWOPS_COLSUM_WIDE, ROWOPS_COLSUM_TALL4, ROWOPS_COLSUM, ROWOPS_LSRES_FWD, ROWOPS_LSRES_BWD_ROWS, ROWOPS_LSRES_BWD,
+       ROWOPS_LSRES_BWD16_V2, ROWOPS_LSRES_BWD16_V4, ROWOPS_ACT_BWD, ROWOPS_DROPOUT };
+struct RowopsPlan { int kernel; long gx, gy, members; };
+static int colsum_plan(long R, int C, long ld, bool aligned, RowopsPlan& p) {
+    p = RowopsPlan{ROWOPS_NONE, 0, 0, 0};
+    if (C <= 0 || R <= 0) return 0;
+    const bool al4 = (C % 4 == 0) && (ld % 4 == 0) && aligned;
     const bool wide = al4 && R <= 64 && C >= 4096;
-    const DetWs ws = spe_detws();
     if (wide) {
-        hipLaunchKernelGGL(colsum_wide_kernel, dim3((unsigned)((C / 4 + 255) / 256)), dim3(256), 0, st, in, out, (int)R, (long)C, ld, accumulate);
+        p = RowopsPlan{ROWOPS_COLSUM_WIDE, (C / 4 + 255) / 256, 1, 0};
     } else if (al4) {
         const int gx = (C / 4 + 15) / 16;
         long ry = (R + 63) / 64;                       // >= 4 rows per thread
         const long cap = (2048 + gx - 1) / gx;         // ~8 blocks per CU overall
         if (ry > cap) ry = cap; if (ry < 1) ry = 1;
-        DET_CHECK(ws, gx, ry, 64);
-        hipLaunchKernelGGL(colsum_tall4_kernel, dim3(gx, (unsigned)ry), dim3(256), 0, st, in, out, R, C, ld, accumulate, ws);
+        p = RowopsPlan{ROWOPS_COLSUM_TALL4, gx, ry, ry};
     } else {
         long ry = (R + 255) / 256; if (ry > 64) ry = 64; if (ry < 1) ry = 1;
-        DET_CHECK(ws, (C + 63) / 64, ry, 64);
-        hipLaunchKernelGGL(colsum_kernel, dim3((C + 63) / 64, (unsigned)ry), dim3(256), 0, st, in, out, R, C, ld, accumulate, ws);
+        p = RowopsPlan{ROWOPS_COLSUM, (C + 63) / 64, ry, ry};
+    }
+    return 0;
+}
+extern "C" int spe_colsum(const float* in, float* out, long R, int C, long ld, int accumulate, hipStream_t st) {
+    if (C <= 0) return 0;
+    if (R <= 0) { if (!accumulate) { hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)C, st); if (e != hipSuccess) return (int)e; } return 0; }
+    RowopsPlan pl;
+    colsum_plan(R, C, ld, (((uintptr_t)in) | ((uintptr_t)out)) % 16 == 0, pl);
+    const DetWs ws = spe_detws();
+    if (pl.kernel == ROWOPS_COLSUM_WIDE) {
+        hipLaunchKernelGGL(colsum_wide_kernel, dim3((unsigned)pl.gx), dim3(256), 0, st, in, out, (int)R, (long)C, ld, accumulate);
+    } else if (pl.kernel == ROWOPS_COLSUM_TALL4) {
+        DET_CHECK(ws, pl.gx, pl.gy, 64);
+        hipLaunchKernelGGL(colsum_tall4_kernel, dim3((unsigned)pl.gx, (unsigned)pl.gy), dim3(256), 0, st, in, out, R, C, ld, accumulate, ws);
+    } else {
+        DET_CHECK(ws, pl.gx, pl.gy, 64);
+        hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)pl.gx, (unsigned)pl.gy), dim3(256), 0, st, in, out, R, C, ld, accumulate, ws);
     }
     SPE_CHECK_LAUNCH();
     return 0;
@@ -686,17 +707,27 @@ __global__ __launch_bounds__(1024) void lsres_bwd16_kernel(const float* __restri
     });
 }
 
+static int lsres_bwd16_plan(long R, int C, long ldt, bool aligned, RowopsPlan& p) {
+    p = RowopsPlan{ROWOPS_NONE, 0, 0, 0};
+    if (R <= 0) return 0;
+    if ((C & 3) || C > 256 * LN_MAXV || (ldt & 63) || ldt < R) return -2;
+    if (!aligned) return -2;
+    // 2 float4 per lane up to C = 512: fewer live registers per wave than the 4 the widest rows need
+    const int variant = C <= 512 ? 0 : 1;
+    long nb = (ldt + 63) / 64; if (nb > 256) nb = 256;
+    p = RowopsPlan{variant == 0 ? ROWOPS_LSRES_BWD16_V2 : ROWOPS_LSRES_BWD16_V4, nb, 1, nb};
+    return 0;
+}
 static int lsres_bwd16_launch(const float* dout, const void* y, int y_f16, const float* gamma, void* dy16, void* dy16T, long ldt,
                               float* db, float* dgamma, long R, int C, float p_drop, uint64_t seed, uint64_t offset, const float* sscale, long rps,
                               hipStream_t st) {
-    if (R <= 0) return 0;
-    if ((C & 3) || C > 256 * LN_MAXV || (ldt & 63) || ldt < R) return -2;
-    if ((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gamma) |
-         reinterpret_cast<uintptr_t>(dy16) | reinterpret_cast<uintptr_t>(dy16T)) & 15) return -2;
+    RowopsPlan pl;
+    const int rc = lsres_bwd16_plan(R, C, ldt, ((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gamma) |
+                                                 reinterpret_cast<uintptr_t>(dy16) | reinterpret_cast<uintptr_t>(dy16T)) & 15) == 0, pl);
+    if (rc != 0 || pl.kernel == ROWOPS_NONE) return rc;
     const int tile_bytes = 64 * (C + 8) * 2, red_bytes = 32 * (C + 4) * 4;
     const int smem = tile_bytes > red_bytes ? tile_bytes : red_bytes;
-    // 2 float4 per lane up to C = 512: fewer live registers per wave than the 4 the widest rows need
-    const int variant = C <= 512 ? 0 : 1;
+    const int variant = pl.kernel == ROWOPS_LSRES_BWD16_V2 ? 0 : 1;
     const auto kernel = variant == 0 ? lsres_bwd16_kernel<2> : lsres_bwd16_kernel<LN_MAXV>;
     static bool attr[2] = {false, false};
     if (!attr[variant]) {
@@ -705,7 +736,7 @@ static int lsres_bwd16_launch(const float* dout, const void* y, int y_f16, const
         if (e != hipSuccess) return (int)e;
         attr[variant] = true;
     }
-    long nb = (ldt + 63) / 64; if (nb > 256) nb = 256;
+    const long nb = pl.gx;
     DetWs ws = spe_detws();
     const DetDeferSeg sg[2] = {{dgamma, C}, {db, C}};
     float* region = det_defer_try(1, nb, 2 * C, 2, sg, st);        // deferred: dgamma / db += totals at the next flush
@@ -732,33 +763,55 @@ extern "C" int spe_layerscale_residual_bwd16d(const float* dout, const void* y, 
                               sample_scale ? rows_per_sample : 1, st);
 }
 
-extern "C" int spe_layerscale_residual_fwd(const float* x, const float* y, const float* gamma, const float* sample_scale,
-                                           float* out, long R, int C, long rows_per_sample, hipStream_t st) {
+static int lsres_fwd_plan(long R, int C, RowopsPlan& p) {
+    p = RowopsPlan{ROWOPS_NONE, 0, 0, 0};
     if (R <= 0) return 0;
     if (C & 3) return -2;
     const long n4 = R * C / 4;
     long nb = (n4 + 255) / 256; if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(lsres_fwd_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const float4*)x, (const float4*)y,
+    p = RowopsPlan{ROWOPS_LSRES_FWD, nb, 1, 0};
+    return 0;
+}
+extern "C" int spe_layerscale_residual_fwd(const float* x, const float* y, const float* gamma, const float* sample_scale,
+                                           float* out, long R, int C, long rows_per_sample, hipStream_t st) {
+    RowopsPlan pl;
+    const int rc = lsres_fwd_plan(R, C, pl);
+    if (rc != 0 || pl.kernel == ROWOPS_NONE) return rc;
+    const long n4 = R * C / 4;
+    hipLaunchKernelGGL(lsres_fwd_kernel, dim3((unsigned)pl.gx), dim3(256), 0, st, (const float4*)x, (const float4*)y,
                        (const float4*)gamma, sample_scale, (float4*)out, n4, C / 4, rows_per_sample * C / 4);
     SPE_CHECK_LAUNCH();
+    return 0;
+}
+static int lsres_bwd_plan(long R, int C, bool aligned, RowopsPlan& p) {
+    p = RowopsPlan{ROWOPS_NONE, 0, 0, 0};
+    if (R <= 0) return 0;
+    if ((C & 3) == 0 && C <= 256 * LN_MAXV && aligned) {
+        long nb = (R + 15) / 16; if (nb > 128) nb = 128;
+        p = RowopsPlan{ROWOPS_LSRES_BWD_ROWS, nb, 1, nb};
+        return 0;
+    }
+    long ry = (R + 63) / 64; if (ry > 256) ry = 256; if (ry < 1) ry = 1;
+    p = RowopsPlan{ROWOPS_LSRES_BWD, (C + 63) / 64, ry, ry};
     return 0;
 }
 extern "C" int spe_layerscale_residual_bwd(const float* dout, const float* y, const float* gamma, const float* sample_scale,
                                            float* dy, float* dgamma, long R, int C, long rows_per_sample, hipStream_t st) {
     if (R <= 0) return 0;
     const DetWs ws = spe_detws();
-    if ((C & 3) == 0 && C <= 256 * LN_MAXV && ((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(y) |
-                                                           reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(gamma)) & 15) == 0) {
-        long nb = (R + 15) / 16; if (nb > 128) nb = 128;
+    RowopsPlan pl;
+    lsres_bwd_plan(R, C, ((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(y) |
+                           reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(gamma)) & 15) == 0, pl);
+    if (pl.kernel == ROWOPS_LSRES_BWD_ROWS) {
+        const long nb = pl.gx;
         DET_CHECK(ws, 1, nb, C);
         hipLaunchKernelGGL(lsres_bwd_rows_kernel<16>, dim3((unsigned)nb), dim3(1024), 16 * (C + 4) * (int)sizeof(float), st, dout, y,
                            gamma, sample_scale, dy, dgamma, R, C, rows_per_sample, ws);
         SPE_CHECK_LAUNCH();
         return 0;
     }
-    long ry = (R + 63) / 64; if (ry > 256) ry = 256; if (ry < 1) ry = 1;
-    DET_CHECK(ws, (C + 63) / 64, ry, 64);
-    hipLaunchKernelGGL(lsres_bwd_kernel, dim3((C + 63) / 64, (unsigned)ry), dim3(256), 0, st, dout, y, gamma, sample_scale,
+    DET_CHECK(ws, pl.gx, pl.gy, 64);
+    hipLaunchKernelGGL(lsres_bwd_kernel, dim3((unsigned)pl.gx, (unsigned)pl.gy), dim3(256), 0, st, dout, y, gamma, sample_scale,
                        dy, dgamma, R, C, rows_per_sample, ws);
     SPE_CHECK_LAUNCH();
     return 0;
@@ -787,11 +840,19 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float4* __restrict__
         dx[i] = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
-extern "C" int spe_act_bwd(const float* dy, const float* aux, float* dx, long n, int mode, hipStream_t st) {
+static int act_bwd_plan(long n, RowopsPlan& p) {
+    p = RowopsPlan{ROWOPS_NONE, 0, 0, 0};
     if (n <= 0) return 0;
     if (n & 3) return -2;
     long nb = (n / 4 + 255) / 256; if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const float4*)dy, (const float4*)aux, (float4*)dx, n / 4, mode);
+    p = RowopsPlan{ROWOPS_ACT_BWD, nb, 1, 0};
+    return 0;
+}
+extern "C" int spe_act_bwd(const float* dy, const float* aux, float* dx, long n, int mode, hipStream_t st) {
+    RowopsPlan pl;
+    const int rc = act_bwd_plan(n, pl);
+    if (rc != 0 || pl.kernel == ROWOPS_NONE) return rc;
+    hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)pl.gx), dim3(256), 0, st, (const float4*)dy, (const float4*)aux, (float4*)dx, n / 4, mode);
     SPE_CHECK_LAUNCH();
     return 0;
 }
@@ -802,10 +863,34 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
         y[i] = x[i] * spe_drop_scale(seed, offset, (uint64_t)i, p);
 }
-extern "C" int spe_dropout(const float* x, float* y, long n, float p, uint64_t seed, uint64_t offset, hipStream_t st) {
+static int dropout_plan(long n, RowopsPlan& p) {
+    p = RowopsPlan{ROWOPS_NONE, 0, 0, 0};
     if (n <= 0) return 0;
     long nb = (n + 255) / 256; if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)nb), dim3(256), 0, st, x, y, n, p, seed, offset);
+    p = RowopsPlan{ROWOPS_DROPOUT, nb, 1, 0};
+    return 0;
+}
+extern "C" int spe_dropout(const float* x, float* y, long n, float p, uint64_t seed, uint64_t offset, hipStream_t st) {
+    RowopsPlan pl;
+    dropout_plan(n, pl);
+    if (pl.kernel == ROWOPS_NONE) return 0;
+    hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)pl.gx), dim3(256), 0, st, x, y, n, p, seed, offset);
     SPE_CHECK_LAUNCH();
     return 0;
+}
+// C-ABI: see include/spe_hip.h (spe_rowops_plan).  Host only.
+extern "C" int spe_rowops_plan(int launcher, long R, int C, long ld, int aligned, long* v) {
+    RowopsPlan p = {ROWOPS_NONE, 0, 0, 0};
+    int rc;
+    switch (launcher) {
+        case 0: rc = colsum_plan(R, C, ld, aligned != 0, p); break;
+        case 1: rc = lsres_fwd_plan(R, C, p); break;
+        case 2: rc = lsres_bwd_plan(R, C, aligned != 0, p); break;
+        case 3: rc = lsres_bwd16_plan(R, C, ld, aligned != 0, p); break;
+        case 4: rc = act_bwd_plan(R, p); break;
+        case 5: rc = dropout_plan(R, p); break;
+        default: rc = -2;
+    }
+    v[0] = p.kernel; v[1] = p.gx; v[2] = p.gy; v[3] = p.members;
+    return rc;
 }

@@ -1166,6 +1166,24 @@ def layerscale_residual_bwd(dout2, y2, gamma, sample_scale, rows_per_sample, dg_
     return dy, dg
 
 
+ROWOPS_LAUNCHERS = ("colsum", "lsres_fwd", "lsres_bwd", "lsres_bwd16", "act_bwd", "dropout")
+ROWOPS_KERNELS = (None, "colsum_wide", "colsum_tall4", "colsum", "lsres_fwd", "lsres_bwd_rows", "lsres_bwd", "lsres_bwd16<2>", "lsres_bwd16<4>",
+                  "act_bwd", "dropout")
+
+
+def rowops_plan(launcher, R, C=0, ld=None, aligned=True):
+    """The kernel and grid a launcher of csrc/rowops.hip (launcher in ROWOPS_LAUNCHERS) chooses for a shape (spe_rowops_plan, the
+    launchers' own functions): dict(kernel (a name of ROWOPS_KERNELS; None: nothing is launched), grid_x, grid_y, members (of the
+    fixed-order sum across workgroups; 0: none), status).  act_bwd / dropout: R is the element count.  ld: row stride of colsum's input,
+    ldt of lsres_bwd16 (default: C, and R rounded up to 64); aligned: the pointers are 16-B aligned.  Needs no device.  For tests and
+    tools: no hot path calls it."""
+    if ld is None:
+        ld = (R + 63) // 64 * 64 if launcher == "lsres_bwd16" else C
+    v = (ctypes.c_long * 4)()
+    rc = lib.load().spe_rowops_plan(ROWOPS_LAUNCHERS.index(launcher), R, C, ld, int(bool(aligned)), v)
+    return dict(kernel=ROWOPS_KERNELS[v[0]], grid_x=int(v[1]), grid_y=int(v[2]), members=int(v[3]), status=rc)
+
+
 # ---- dropout --------------------------------------------------------------------------------
 def dropout(x, p, seed, offset):
     _chk(x)
