@@ -250,8 +250,7 @@ __global__ __launch_bounds__(64 * FLF_NW, FLF_NW / 4) void talking_flash_fwd_ker
 
         // ---- partial O of this segment -> the major's slot (fragment order: one coalesced 1-KB store per accumulator register group)
         if (wvalid) {
-            const int first_wg = (int)(((long)bm * nt) / a.spw);
-            const int slot = (int)blockIdx.x - first_wg;
+            const int slot = fl_slot(bm, nt, a.spw);
 #pragma unroll
             for (int u = 0; u < QS; ++u) {
                 if (qt0 + u >= nt) continue;

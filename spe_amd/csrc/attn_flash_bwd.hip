@@ -22,6 +22,18 @@
 // attn_flash_common.h (fl_plan) with 4 tiles per workgroup; partial D / dQ / dV of a segment go to slot workspaces summed in fixed order by the
 // small merge kernels below (bitwise reproducible, no atomics).
 //
+// Written once for both kernels (what each piece costs, and what was tried and taken out again: profiles/attn_bwd_one_skeleton.txt):
+//   flb_lds               the LDS layout: the kernel bodies take their offsets from it, the host its byte counts
+//   flb_back_exp, flb_dp_mix, flb_gw_product: the exponentials, the tail of the dP' -> dP head mix, the 8 packet pairs of the outer product
+//   FLB_RS_G0 .. G7       the 32 DPP adds of the D reduce-scatter, alone (flb_rowsum4) or between matrix instructions (FLB_SCORE_RS_ASM)
+//   fl_slot               (attn_flash_common.h, with the flash forward) the slot of a segment's partial result
+//   flb_fill, flb_dispatch: the checks, the plan, the shared argument fields and the launch of the two entry points
+// Contract: a shared piece owns no scheduling decision and leaves the compiled kernels as they were - each of the above leaves all 30 kernels of this file
+// without one differing line of assembly.  Each kernel keeps its own `step` (what runs beside what, the sched_barriers between the regions, the s_memtime
+// stamps), its ONE loop instance, its inline assembly with "a" constraints.  What still stands twice - the plan decode, the piece offsets and piece loop,
+// the resident and fragment loads, admit, the transpose-tile set-up, the accumulator product and the slot store - stands twice on purpose: hoisted, each
+// changed the compiled code of these one-wave-per-SIMD kernels, and two of them a timed line (same record).
+//
 // What was tried on these loops and lost (exponentials inside an inline-assembly mix block, the reduce-scatter from DPP builtins,
 // sched_group_barrier interleave requests, the back half first in source order, a query-major pass 1): profiles/HISTORY_r05.md.
 // Timing ablations (-DSPE_ABLATE builds only, tools/ab.py): FLB_DBG_SAMETILE (every workgroup streams tile 0: all L2 hits), FLB_DBG_NOST (no dS store).
@@ -50,6 +62,25 @@
 #ifndef FLB_STAGGER
 #define FLB_STAGGER 1                    // waves 2, 3 issue their share of the next tile's loads one scheduling region later than waves 0, 1
 #endif
+
+// ---- LDS of a workgroup, stated ONCE for the kernel bodies and the host: byte offsets from the start of the dynamic LDS, in this order.
+//   two stages of the two streamed 32-wide tiles (a tile: one operand, 16 rows, all heads = H records of DT * 512 B) ; s16: FLB_NK16 slots of the
+//   streamed 16-wide tile ; key-major kernel only: c0, two stages of row constants (1 KB each), and dx, the D exchange 2 x FLB_NW x (16 H floats) ;
+//   gconst: 512 B of constants (zeros at + 48, bf16 ones at + 208, 128 B each) ; gw: FLB_NW x 3 transpose tiles of gwt B (4 H rows of FLB_GWR B) ;
+//   kb: with dropout two stages of keep-flag records (1 KB: the four waves' 256 B each) ; bytes: the total
+struct FlbLds { int tile, stage, s16, c0, dx, gconst, gw, gwt, kb, bytes; };
+constexpr FlbLds flb_lds(int H, int DT, bool keymajor, bool drop) {
+    FlbLds l{};
+    l.tile = H * DT * 512; l.stage = 2 * l.tile;
+    l.s16 = 2 * l.stage;
+    l.c0 = l.s16 + FLB_NK16 * l.tile;
+    l.dx = l.c0 + (keymajor ? 2048 : 0);
+    l.gconst = l.dx + (keymajor ? 2 * FLB_NW * 16 * H * 4 : 0);
+    l.gw = l.gconst + 512; l.gwt = 4 * H * FLB_GWR;
+    l.kb = l.gw + FLB_NW * 3 * l.gwt;
+    l.bytes = l.kb + (drop ? 2048 : 0);
+    return l;
+}
 
 struct FlashBwdArgs {
     const unsigned char* Qf; const unsigned char* dOf;            // q-side fragment records (fp16 q * scale * log2 e ; bf16 dO)
@@ -127,15 +158,56 @@ __device__ __forceinline__ void flb_dq_mfma(f32x4_t* acc, const fls16x4_t* ka, f
 // the accumulators become readable (segment end)
 __device__ __forceinline__ void flb_acc_fence(f32x4_t& a) { asm volatile("s_nop 7\n\ts_nop 4" : "+a"(a)); }
 
+// =====================================================================================================================================
+// The pieces both kernels are built from (contract in the file header).  None of them holds a scheduling barrier: what runs beside what stays in the
+// kernels' step lambdas.
+// ---- P = exp2(sp) in place (P * 2^8 in the key-major kernel, whose exponent starts 8 higher)
+template <int H>
+__device__ __forceinline__ void flb_back_exp(f32x4_t (&sp)[4][H / 4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int gh = 0; gh < H / 4; ++gh)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sp[r][gh][k] = fl_exp2(sp[r][gh][k]);
+}
+// ---- dP += Ww^T dP' for the chunk of HB heads from head G0 (es: their dP' after dropout)
+template <int H, int HB, int G0>
+__device__ __forceinline__ void flb_dp_mix(const f32x4_t (&es)[HB], const fls16x4_t (&Awt)[H / 4][H / 4], f32x4_t (&dp)[4][H / 4]) {
+#pragma unroll
+    for (int hq = 0; hq < HB / 4; ++hq)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const fls16x4_t bv = fl_pack4<false>(es[4 * hq][r], es[4 * hq + 1][r], es[4 * hq + 2][r], es[4 * hq + 3][r]);
+#pragma unroll
+            for (int gh = 0; gh < H / 4; ++gh) dp[r][gh] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(Awt[gh][G0 / 4 + hq], bv, dp[r][gh], 0, 0, 0);
+        }
+}
+// ---- the 8 packet pairs of one tile of the weight-gradient outer product between the wave fences (talking_bwdq_kernel has the story): acc += X Y^T with
+// the lane's 16 packets of X at xrd and of Y at yrd.  The callers choose the pointers: which operand is the double-buffered front one, and which lanes
+// read the zeros or the ones block instead of a row.
+__device__ __forceinline__ void flb_gw_product(const unsigned char* xrd, const unsigned char* yrd, f32x4_t (&acc)[4]) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // wave-private tile: the other lanes' packets are read next
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const flu32x4_t xa = *reinterpret_cast<const flu32x4_t*>(xrd + c * 16);
+        const flu32x4_t yb = *reinterpret_cast<const flu32x4_t*>(yrd + c * 16);
+        // one 32-deep instruction per 16-B packet pair: a contraction over positions does not care which 8 positions a lane group brings
+        // (the 16-deep form costs the same issue slot for half the positions: profiles/r05_mfma_form.txt)
+        acc[c & 3] = fl_mfma32<false>(xa, yb, acc[c & 3]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the back tile is rewritten by the next streamed tile
+}
+
 template <int H, int DSTEPS, bool TAIL16, bool DROP>
 __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdArgs a) {
     constexpr int FULL = FragDims<DSTEPS, TAIL16>::FULL, DT = FragDims<DSTEPS, TAIL16>::DT, REC = FragDims<DSTEPS, TAIL16>::REC;
     constexpr int NW = FLB_NW, HB = (H >= FLB_HB) ? FLB_HB : H;
-    constexpr int TILEB = H * REC;                  // one operand, one 16-row tile, all heads
-    constexpr int KVB = 2 * TILEB;                  // a K / V stage: K fragments, V fragments
+    constexpr FlbLds L = flb_lds(H, DT, false, DROP);       // a stage: K fragments, V fragments ; the 16-wide slots: K
+    constexpr int TILEB = L.tile, KVB = L.stage, GWT = L.gwt, KBOFF = L.kb;
     constexpr int NK16 = FLB_NK16;
     constexpr int F1 = FULL ? FULL : 1;
-    // LDS: [K / V stage 0][K / V stage 1][FLB_NK16 slots of K in the 16-wide layout][constants 512 B][NW x 3 transpose tiles]
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem);
@@ -158,10 +230,9 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdAr
     // reads of 8 heads fall on 2 bank groups (4-way conflicts: SQ_LDS_BANK_CONFLICT was half of the LDS cycles of the round-3 passes); 144 B
     // spreads the 8 rows of a lane group over distinct banks, and the constant blocks sit on banks no row uses.  The operand the FRONT half
     // of a tile writes (here Y, in the key-major kernel X) is double-buffered by tile parity: the front half of tile j + 1 runs beside the back half of tile j.
-    constexpr int GWR = FLB_GWR, GWT = 4 * H * GWR;
-    unsigned char* gconst = smem + 2 * KVB + NK16 * TILEB;                  // 512 B: zeros at + 48 (128 B), bf16 ones at + 208 (128 B)
-    constexpr int KBOFF = 2 * KVB + NK16 * TILEB + 512 + NW * 3 * GWT;     // dropout: 2 x 1 KB of keep-flag records (the four waves' 256 B of a key tile each), behind the transpose tiles
-    unsigned char* sgw = gconst + 512 + wave * (3 * GWT);                   // [front operand, parity 0][front operand, parity 1][back operand]
+    constexpr int GWR = FLB_GWR;
+    unsigned char* gconst = smem + L.gconst;
+    unsigned char* sgw = smem + L.gw + wave * (3 * GWT);                    // [front operand, parity 0][front operand, parity 1][back operand]
     if (threadIdx.x < 64) reinterpret_cast<uint2*>(gconst)[threadIdx.x] = (threadIdx.x >= 26 && threadIdx.x < 42) ? make_uint2(0x3F803F80u, 0x3F803F80u) : make_uint2(0u, 0u);
     const int gm = lane & 15, gk = lane >> 4;
     unsigned char* gw_wr = sgw + (gk * H) * GWR + gm * 8;                   // + tile * GWT + h * GWR: packet of head h, query gm, key group gk
@@ -247,7 +318,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdAr
             for (int op = 0; op < 3; ++op) {
                 const unsigned char* base = (op == 0) ? a.Kf : ((op == 1) ? a.Vf : a.K16);
                 const unsigned char* tb = base + ((long)b * H * nt + kt) * REC;
-                const unsigned dst = (op < 2) ? lds0 + (i & 1) * KVB + op * TILEB : lds0 + 2 * KVB + (i % NK16) * TILEB;
+                const unsigned dst = (op < 2) ? lds0 + (i & 1) * KVB + op * TILEB : lds0 + L.s16 + (i % NK16) * TILEB;
                 if constexpr (NP % NW == 0 && NPW <= 4) fl_glds16_run<NPW, NW * 1024>(tb, voff, dst + wave * 1024);
                 else {
 #pragma unroll
@@ -333,14 +404,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdAr
                     for (int r = 0; r < 4; ++r) es[hb][r] *= ((kb >> ((g >> 1) * 8 + 2 * r + (g & 1))) & 1u) ? keep_inv : 0.f;
                 }
             }
-#pragma unroll
-            for (int hq = 0; hq < HB / 4; ++hq)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const fls16x4_t bv = fl_pack4<false>(es[4 * hq][r], es[4 * hq + 1][r], es[4 * hq + 2][r], es[4 * hq + 3][r]);
-#pragma unroll
-                    for (int gh = 0; gh < H / 4; ++gh) dp[r][gh] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(Awt[gh][g0 / 4 + hq], bv, dp[r][gh], 0, 0, 0);
-                }
+            flb_dp_mix<H, HB, g0>(es, Awt, dp);
         };
         auto load_kb = [&](int i) -> uint32_t {
             if constexpr (DROP) return *reinterpret_cast<const uint32_t*>(smem + KBOFF + (i & 1) * 1024 + wave * 256 + lane * 4);
@@ -352,14 +416,6 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdAr
         //   back_ds : dS' = P (dP - D), dbl, bf16(dS') -> transpose tile
         //   back_gw : the outer product dWl from the transpose tiles ; dS = Wl^T dS' -> ds
         //   back_dq : bf16 block of dS -> HBM, dQ^T += K^T dS^T
-        auto back_exp = [&](f32x4_t (&sp)[4][H / 4]) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int gh = 0; gh < H / 4; ++gh)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) sp[r][gh][k] = fl_exp2(sp[r][gh][k]);
-        };
         auto back_ds = [&](f32x4_t (&sp)[4][H / 4], f32x4_t (&dp)[4][H / 4]) {
             unsigned char* gwb = gw_wr + 2 * GWT;               // the back operand of the outer product
 #pragma unroll
@@ -378,20 +434,8 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdAr
         auto back_gw = [&](int i, f32x4_t (&sp)[4][H / 4], f32x4_t (&ds)[4][H / 4]) {
             {
                 const unsigned rdf = gw_rd + (i & 1) * GWT, rdb = gw_rd + 2 * GWT;
-                // lanes >= H of a 16-lane group read zeros
-                const unsigned char* gw_xrd = (gm < H) ? sgw + rdb : gw_zero;
-                const unsigned char* gw_yrd = (gm < H) ? sgw + rdf : gw_zero;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // wave-private tile: the other lanes' packets are read next
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const flu32x4_t xa = *reinterpret_cast<const flu32x4_t*>(gw_xrd + c * 16);
-                    const flu32x4_t yb = *reinterpret_cast<const flu32x4_t*>(gw_yrd + c * 16);
-                    // one 32-deep instruction per 16-B packet pair: a contraction over positions does not care which 8 positions a lane group brings
-                    // (the 16-deep form costs the same issue slot for half the positions: profiles/r05_mfma_form.txt)
-                    gwacc[c & 3] = fl_mfma32<false>(xa, yb, gwacc[c & 3]);
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the back tile is rewritten by the next key tile
+                // X = dS' (back operand), Y = S (front operand) ; lanes >= H of a 16-lane group read zeros
+                flb_gw_product((gm < H) ? sgw + rdb : gw_zero, (gm < H) ? sgw + rdf : gw_zero, gwacc);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -404,7 +448,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdAr
         auto back_dq = [&](int i, f32x4_t (&ds)[4][H / 4]) {
             {
                 const int kt = kt0 + i;
-                const unsigned char* sK16 = smem + 2 * KVB + (i % NK16) * TILEB;
+                const unsigned char* sK16 = smem + L.s16 + (i % NK16) * TILEB;
                 fls16x4_t ka[H][DT];                // requested FLB_DQAHEAD heads ahead of the matrix instructions that consume them
 #pragma unroll
                 for (int h = 0; h < ((FLB_DQAHEAD < H) ? FLB_DQAHEAD : H); ++h)
@@ -441,7 +485,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdAr
         };
         auto back = [&](int i, f32x4_t (&sp)[4][H / 4], f32x4_t (&dp)[4][H / 4]) {
             f32x4_t ds[4][H / 4];
-            back_exp(sp);
+            flb_back_exp<H>(sp);
             back_ds(sp, dp);
             back_gw(i, sp, ds);
             back_dq(i, ds);
@@ -458,7 +502,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdAr
             if constexpr (H > HB) load_k(i + 1, HB, fr1); else load_v(i + 1, 0, fr1);
             __builtin_amdgcn_sched_barrier(FLB_SB_NOMEM);
             front_k(i + 1, std::integral_constant<int, 0>{}, fr0, spn, std::false_type{});
-            back_exp(sp);
+            flb_back_exp<H>(sp);
             FLB_PHASE();
             FLB_STAMP(2);
             // the late half of the workgroup's tile loads (see admit)
@@ -535,8 +579,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdq_kernel(FlashBwdAr
         __builtin_amdgcn_s_barrier();              // the last buffers have been read by everybody: the next segment may refill them
 
         // ---- partial results of this segment -> the major's slot
-        const int first_wg = (int)(((long)bm * nt) / a.spw);
-        const int slot = (int)blockIdx.x - first_wg;
+        const int slot = fl_slot(bm, nt, a.spw);
         {
 #pragma unroll
             for (int g = 0; g < H; ++g)
@@ -653,45 +696,26 @@ struct FlashBwdKArgs {
 //   even / odd bank of each half (partner: the mirrored lane of the other bank) ; then the quad's four lanes add up (xor 1, xor 2).
 // Every instruction reads registers written at least three instructions earlier (a DPP read needs two wait states behind a vector write);
 // the leading s_nop covers the products computed just before.
+// The 32 adds, written once as eight groups of four: FLB_DPP4(D, S, CTL) is D[k] = S[k] + CTL(S[k]) for k = 0 .. 3 on the named asm operands D0 .. D3, S0 .. S3.
+// a / b: the two halves' partial sums, o: the result, t0 .. t3: the terms of query rows 0 .. 3.  Each group opens with its own line break, so a matrix
+// instruction (FLB_SCORE_RS_ASM) or nothing (flb_rowsum4) can stand between two groups.
+#define FLB_DPP1(D, S, K, CTL) "\n\tv_add_f32_dpp %[" D K "], %[" S K "], %[" S K "] " CTL
+#define FLB_DPP4(D, S, CTL) FLB_DPP1(D, S, "0", CTL) FLB_DPP1(D, S, "1", CTL) FLB_DPP1(D, S, "2", CTL) FLB_DPP1(D, S, "3", CTL)
+#define FLB_RS_G0 FLB_DPP4("a", "t0", "row_ror:8 row_mask:0xf bank_mask:0x3")
+#define FLB_RS_G1 FLB_DPP4("a", "t2", "row_ror:8 row_mask:0xf bank_mask:0xc")
+#define FLB_RS_G2 FLB_DPP4("b", "t1", "row_ror:8 row_mask:0xf bank_mask:0x3")
+#define FLB_RS_G3 FLB_DPP4("b", "t3", "row_ror:8 row_mask:0xf bank_mask:0xc")
+#define FLB_RS_G4 FLB_DPP4("o", "a", "row_half_mirror row_mask:0xf bank_mask:0x5")
+#define FLB_RS_G5 FLB_DPP4("o", "b", "row_half_mirror row_mask:0xf bank_mask:0xa")
+#define FLB_RS_G6 FLB_DPP4("o", "o", "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
+#define FLB_RS_G7 FLB_DPP4("o", "o", "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
+#define FLB_RS_OUTS [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [b0] "=&v"(b0), [b1] "=&v"(b1), [b2] "=&v"(b2), [b3] "=&v"(b3), \
+                    [o0] "=&v"(o[0]), [o1] "=&v"(o[1]), [o2] "=&v"(o[2]), [o3] "=&v"(o[3])
+#define FLB_RS_INS [t00] "v"(t[0][0]), [t01] "v"(t[0][1]), [t02] "v"(t[0][2]), [t03] "v"(t[0][3]), [t10] "v"(t[1][0]), [t11] "v"(t[1][1]), [t12] "v"(t[1][2]), [t13] "v"(t[1][3]), \
+                   [t20] "v"(t[2][0]), [t21] "v"(t[2][1]), [t22] "v"(t[2][2]), [t23] "v"(t[2][3]), [t30] "v"(t[3][0]), [t31] "v"(t[3][1]), [t32] "v"(t[3][2]), [t33] "v"(t[3][3])
 __device__ __forceinline__ void flb_rowsum4(const f32x4_t (&t)[4], f32x4_t& o) {
     float a0, a1, a2, a3, b0, b1, b2, b3;
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %12, %12 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_f32_dpp %1, %13, %13 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_f32_dpp %2, %14, %14 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_f32_dpp %3, %15, %15 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_f32_dpp %0, %20, %20 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %1, %21, %21 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %2, %22, %22 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %3, %23, %23 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %4, %16, %16 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_f32_dpp %5, %17, %17 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_f32_dpp %6, %18, %18 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_f32_dpp %7, %19, %19 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_f32_dpp %4, %24, %24 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %5, %25, %25 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %6, %26, %26 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %7, %27, %27 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %8, %0, %0 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_f32_dpp %9, %1, %1 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_f32_dpp %10, %2, %2 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_f32_dpp %11, %3, %3 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_f32_dpp %8, %4, %4 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_f32_dpp %9, %5, %5 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_f32_dpp %10, %6, %6 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_f32_dpp %11, %7, %7 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_f32_dpp %8, %8, %8 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %9, %9, %9 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %10, %10, %10 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %11, %11, %11 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %8, %8, %8 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %9, %9, %9 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %10, %10, %10 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %11, %11, %11 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
-        : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3),
-          "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3])
-        : "v"(t[0][0]), "v"(t[0][1]), "v"(t[0][2]), "v"(t[0][3]), "v"(t[1][0]), "v"(t[1][1]), "v"(t[1][2]), "v"(t[1][3]),
-          "v"(t[2][0]), "v"(t[2][1]), "v"(t[2][2]), "v"(t[2][3]), "v"(t[3][0]), "v"(t[3][1]), "v"(t[3][2]), "v"(t[3][3]));
+    asm("s_nop 1" FLB_RS_G0 FLB_RS_G1 FLB_RS_G2 FLB_RS_G3 FLB_RS_G4 FLB_RS_G5 FLB_RS_G6 FLB_RS_G7 : FLB_RS_OUTS : FLB_RS_INS);
 }
 
 // The score products of a chunk of 4 heads at head dim 33 .. 48 (8 matrix instructions: flb_score_*<1, true>) with the row-sum reduce-scatter of 4 heads
@@ -701,53 +725,14 @@ __device__ __forceinline__ void flb_rowsum4(const f32x4_t (&t)[4], f32x4_t& o) {
     __device__ __forceinline__ void NAME(const flu32x4_t (*k32)[1], const flu32x2_t* k16, const flu32x4_t (*q32)[1], const flu32x2_t* q16, \
                                          f32x4_t* c, const f32x4_t (&t)[4], f32x4_t& o) {                                                  \
         float a0, a1, a2, a3, b0, b1, b2, b3;                                                                                              \
-            asm("s_nop 1\n\t"   \
-                M32 " %0, %16, %24, 0\n\t"   \
-                "v_add_f32_dpp %4, %32, %32 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"   \
-                "v_add_f32_dpp %5, %33, %33 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"   \
-                "v_add_f32_dpp %6, %34, %34 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"   \
-                "v_add_f32_dpp %7, %35, %35 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"   \
-                M32 " %1, %17, %25, 0\n\t"   \
-                "v_add_f32_dpp %4, %40, %40 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"   \
-                "v_add_f32_dpp %5, %41, %41 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"   \
-                "v_add_f32_dpp %6, %42, %42 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"   \
-                "v_add_f32_dpp %7, %43, %43 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"   \
-                M32 " %2, %18, %26, 0\n\t"   \
-                "v_add_f32_dpp %8, %36, %36 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"   \
-                "v_add_f32_dpp %9, %37, %37 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"   \
-                "v_add_f32_dpp %10, %38, %38 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"   \
-                "v_add_f32_dpp %11, %39, %39 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"   \
-                M32 " %3, %19, %27, 0\n\t"   \
-                "v_add_f32_dpp %8, %44, %44 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"   \
-                "v_add_f32_dpp %9, %45, %45 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"   \
-                "v_add_f32_dpp %10, %46, %46 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"   \
-                "v_add_f32_dpp %11, %47, %47 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"   \
-                M16 " %0, %20, %28, %0\n\t"   \
-                "v_add_f32_dpp %12, %4, %4 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"   \
-                "v_add_f32_dpp %13, %5, %5 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"   \
-                "v_add_f32_dpp %14, %6, %6 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"   \
-                "v_add_f32_dpp %15, %7, %7 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"   \
-                M16 " %1, %21, %29, %1\n\t"   \
-                "v_add_f32_dpp %12, %8, %8 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"   \
-                "v_add_f32_dpp %13, %9, %9 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"   \
-                "v_add_f32_dpp %14, %10, %10 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"   \
-                "v_add_f32_dpp %15, %11, %11 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"   \
-                M16 " %2, %22, %30, %2\n\t"   \
-                "v_add_f32_dpp %12, %12, %12 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"   \
-                "v_add_f32_dpp %13, %13, %13 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"   \
-                "v_add_f32_dpp %14, %14, %14 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"   \
-                "v_add_f32_dpp %15, %15, %15 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"   \
-                M16 " %3, %23, %31, %3\n\t"   \
-                "v_add_f32_dpp %12, %12, %12 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"   \
-                "v_add_f32_dpp %13, %13, %13 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"   \
-                "v_add_f32_dpp %14, %14, %14 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"   \
-                "v_add_f32_dpp %15, %15, %15 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"   \
-            : "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]), "=&v"(c[3]), "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(b0), "=&v"(b1), "=&v"(b2),  \
-              "=&v"(b3), "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3])                                                                 \
+        asm("s_nop 1"                                                                                                                      \
+            "\n\t" M32 " %0, %16, %24, 0" FLB_RS_G0 "\n\t" M32 " %1, %17, %25, 0" FLB_RS_G1                                                \
+            "\n\t" M32 " %2, %18, %26, 0" FLB_RS_G2 "\n\t" M32 " %3, %19, %27, 0" FLB_RS_G3                                                \
+            "\n\t" M16 " %0, %20, %28, %0" FLB_RS_G4 "\n\t" M16 " %1, %21, %29, %1" FLB_RS_G5                                              \
+            "\n\t" M16 " %2, %22, %30, %2" FLB_RS_G6 "\n\t" M16 " %3, %23, %31, %3" FLB_RS_G7                                              \
+            : "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]), "=&v"(c[3]), FLB_RS_OUTS                                                              \
             : "v"(k32[0][0]), "v"(k32[1][0]), "v"(k32[2][0]), "v"(k32[3][0]), "v"(k16[0]), "v"(k16[1]), "v"(k16[2]), "v"(k16[3]),          \
-              "a"(q32[0][0]), "a"(q32[1][0]), "a"(q32[2][0]), "a"(q32[3][0]), "a"(q16[0]), "a"(q16[1]), "a"(q16[2]), "a"(q16[3]),          \
-              "v"(t[0][0]), "v"(t[0][1]), "v"(t[0][2]), "v"(t[0][3]), "v"(t[1][0]), "v"(t[1][1]), "v"(t[1][2]), "v"(t[1][3]),              \
-              "v"(t[2][0]), "v"(t[2][1]), "v"(t[2][2]), "v"(t[2][3]), "v"(t[3][0]), "v"(t[3][1]), "v"(t[3][2]), "v"(t[3][3]));             \
+              "a"(q32[0][0]), "a"(q32[1][0]), "a"(q32[2][0]), "a"(q32[3][0]), "a"(q16[0]), "a"(q16[1]), "a"(q16[2]), "a"(q16[3]), FLB_RS_INS); \
     }
 FLB_SCORE_RS_ASM(flb_score_rs_f16, "v_mfma_f32_16x16x32_f16", "v_mfma_f32_16x16x16_f16")
 FLB_SCORE_RS_ASM(flb_score_rs_bf16, "v_mfma_f32_16x16x32_bf16", "v_mfma_f32_16x16x16_bf16")
@@ -758,17 +743,14 @@ template <int H, int DSTEPS, bool TAIL16, bool DROP>
 __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKArgs a) {
     constexpr int FULL = FragDims<DSTEPS, TAIL16>::FULL, DT = FragDims<DSTEPS, TAIL16>::DT, REC = FragDims<DSTEPS, TAIL16>::REC;
     constexpr int NW = FLB_NW, HB = (H >= FLB_HB) ? FLB_HB : H;
-    constexpr int TILEB = H * REC;                  // one operand, one 16-row tile, all heads
-    constexpr int STG = 2 * TILEB;                  // a stage: Q fragments, dO fragments
+    constexpr FlbLds L = flb_lds(H, DT, true, DROP);        // a stage: Q fragments, dO fragments ; the 16-wide slots: dO
+    constexpr int TILEB = L.tile, STG = L.stage, GWT = L.gwt, C0OFF = L.c0, DXOFF = L.dx, DXB = 16 * H * 4, KBOFF = L.kb;
     constexpr int NK16 = FLB_NK16;
     constexpr int F1 = FULL ? FULL : 1;
-    // LDS: [stage 0][stage 1][NK16 slots of dO in the 16-wide layout][c0 rows 2 x 1 KB][D exchange 2 x NW x (16 H floats)][constants 512 B][NW x 3 transpose tiles]
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem);
     const int nt = a.nt;
-    constexpr int C0OFF = 2 * STG + NK16 * TILEB, DXB = 16 * H * 4, DXOFF = C0OFF + 2048, GCOFF = DXOFF + 2 * NW * DXB;
-    constexpr int KBOFF = GCOFF + 512 + NW * 3 * (4 * H * FLB_GWR);       // dropout: 2 x 1 KB of keep-flag records behind the transpose tiles (talking_bwdq_kernel)
 
     float Al4[H / 4][H];                            // S' = Wl S (fp32, 4x4x1)
     fl_mixA_f32<H, false>(a.Wl, lane, Al4);
@@ -785,9 +767,9 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKA
         for (int i = 0; i < 4; ++i) vbw[gh][i] = a.bw[4 * gh + i] * FL_PD_SCALE;
 
     // weight-gradient outer products: X = dP' (front operand, double-buffered by tile parity), Y = P (back operand) - see talking_bwdq_kernel
-    constexpr int GWR = FLB_GWR, GWT = 4 * H * GWR;
-    unsigned char* gconst = smem + GCOFF;
-    unsigned char* sgw = gconst + 512 + wave * (3 * GWT);
+    constexpr int GWR = FLB_GWR;
+    unsigned char* gconst = smem + L.gconst;
+    unsigned char* sgw = smem + L.gw + wave * (3 * GWT);
     if (threadIdx.x < 64) reinterpret_cast<uint2*>(gconst)[threadIdx.x] = (threadIdx.x >= 26 && threadIdx.x < 42) ? make_uint2(0x3F803F80u, 0x3F803F80u) : make_uint2(0u, 0u);
     const int gm = lane & 15, gk = lane >> 4;
     unsigned char* gw_wr = sgw + (gk * H) * GWR + gm * 8;
@@ -863,7 +845,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKA
             for (int op = 0; op < 3; ++op) {
                 const unsigned char* base = (op == 0) ? a.Qf : ((op == 1) ? a.dOf : a.dO16);
                 const unsigned char* tb = base + ((long)b * H * nt + qt) * REC;
-                const unsigned dst = (op < 2) ? lds0 + (i & 1) * STG + op * TILEB : lds0 + 2 * STG + (i % NK16) * TILEB;
+                const unsigned dst = (op < 2) ? lds0 + (i & 1) * STG + op * TILEB : lds0 + L.s16 + (i % NK16) * TILEB;
                 if constexpr (NP % NW == 0 && NPW <= 4) fl_glds16_run<NPW, NW * 1024>(tb, voff, dst + wave * 1024);
                 else {
 #pragma unroll
@@ -947,14 +929,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKA
                 // bf16(dP') of this head: the X operand of the dWw outer product
                 *reinterpret_cast<fls16x4_t*>(gwf + (g0 + hb) * GWR) = fl_pack4<false>(es[hb][0], es[hb][1], es[hb][2], es[hb][3]);
             }
-#pragma unroll
-            for (int hq = 0; hq < HB / 4; ++hq)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const fls16x4_t bv = fl_pack4<false>(es[4 * hq][r], es[4 * hq + 1][r], es[4 * hq + 2][r], es[4 * hq + 3][r]);
-#pragma unroll
-                    for (int gh = 0; gh < H / 4; ++gh) dp[r][gh] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(Awt[gh][g0 / 4 + hq], bv, dp[r][gh], 0, 0, 0);
-                }
+            flb_dp_mix<H, HB, g0>(es, Awt, dp);
         };
         auto load_kb = [&](int i, uint32_t (&kb)[4]) {
             if constexpr (DROP) {
@@ -968,14 +943,6 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKA
         };
 
         // ---- BACK half of q-tile i (vector-heavy)
-        auto back_exp = [&](f32x4_t (&sp)[4][H / 4]) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int gh = 0; gh < H / 4; ++gh)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) sp[r][gh][k] = fl_exp2(sp[r][gh][k]);
-        };
         // D of q-tile i, head group gh: the lane's terms dP P ; the reduced sums -> this wave's block of the exchange buffer
         auto d_terms = [&](int gh, f32x4_t (&sp)[4][H / 4], f32x4_t (&dp)[4][H / 4], f32x4_t (&t)[4]) {
 #pragma unroll
@@ -1006,19 +973,8 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKA
         auto back_gw = [&](int i, f32x4_t (&sp)[4][H / 4], f32x4_t (&pp)[4][H / 4]) {
             {
                 const unsigned rdf = gw_rd + (i & 1) * GWT, rdb = gw_rd + 2 * GWT;
-                const unsigned char* gw_xrd = (gm < H) ? sgw + rdf : gw_zero;
-                const unsigned char* gw_yrd = (gm < H) ? sgw + rdb : ((gm == H) ? gw_ones : gw_zero);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const flu32x4_t xa = *reinterpret_cast<const flu32x4_t*>(gw_xrd + c * 16);
-                    const flu32x4_t yb = *reinterpret_cast<const flu32x4_t*>(gw_yrd + c * 16);
-                    // one 32-deep instruction per 16-B packet pair: a contraction over positions does not care which 8 positions a lane group brings
-                    // (the 16-deep form costs the same issue slot for half the positions: profiles/r05_mfma_form.txt)
-                    gwacc[c & 3] = fl_mfma32<false>(xa, yb, gwacc[c & 3]);
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                // X = dP' (front operand), Y = P (back operand) with the ones row m = H ; lanes of the other rows m >= H read zeros
+                flb_gw_product((gm < H) ? sgw + rdf : gw_zero, (gm < H) ? sgw + rdb : ((gm == H) ? gw_ones : gw_zero), gwacc);
             }
             // P' 2^8 = Ww (P 2^8) + bw 2^8 on fp16 operands (P 2^8 <= 256: no saturation needed)
 #pragma unroll
@@ -1037,7 +993,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKA
             }
         };
         auto back_dv = [&](int i, f32x4_t (&pp)[4][H / 4], const uint32_t (&kb)[4]) {
-            const unsigned char* sD16 = smem + 2 * STG + (i % NK16) * TILEB;
+            const unsigned char* sD16 = smem + L.s16 + (i % NK16) * TILEB;
             fls16x4_t da[H][DT];                // requested FLB_DQAHEAD heads ahead of the matrix instructions that consume them
 #pragma unroll
             for (int h = 0; h < ((FLB_DQAHEAD < H) ? FLB_DQAHEAD : H); ++h)
@@ -1085,7 +1041,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKA
         };
         auto back = [&](int i, f32x4_t (&sp)[4][H / 4], f32x4_t (&dp)[4][H / 4], const uint32_t (&kb)[4]) {
             f32x4_t pp[4][H / 4];
-            back_exp(sp);
+            flb_back_exp<H>(sp);
             back_ds(i, sp, dp);
             back_gw(i, sp, pp);
             back_dv(i, pp, kb);
@@ -1098,7 +1054,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKA
             if constexpr (H > HB) load_q(i + 1, HB, fr1); else load_d(i + 1, 0, fr1);
             __builtin_amdgcn_sched_barrier(FLB_SB_NOMEM);
             front_q(i + 1, std::integral_constant<int, 0>{}, fr0, spn);
-            back_exp(sp);
+            flb_back_exp<H>(sp);
             FLB_PHASE();
             FLB_STAMP(3);
             if (FLB_STAGGER && more && wave >= NW / 2) issue_tiles(i + 2);       // the late half of the workgroup's tile loads (talking_bwdq_kernel: admit)
@@ -1170,8 +1126,7 @@ __global__ __launch_bounds__(64 * FLB_NW, 1) void talking_bwdk_kernel(FlashBwdKA
         d_flush(seg - 1);
 
         // ---- partial dV of this segment -> the major's slot
-        const int first_wg = (int)(((long)bm * nt) / a.spw);
-        const int slot = (int)blockIdx.x - first_wg;
+        const int slot = fl_slot(bm, nt, a.spw);
 #pragma unroll
         for (int g = 0; g < H; ++g)
 #pragma unroll
@@ -1229,23 +1184,18 @@ __global__ __launch_bounds__(256) void bwdk_rows_merge_kernel(const float* __res
     out[i] = acc;
 }
 
-// LDS of a workgroup of the query-major kernel: two stages of the two streamed 32-wide tiles, FLB_NK16 slots of the 16-wide tile (each H records of
-// DT * 512 B), the constants, the weight-gradient transpose tiles of the FLB_NW waves and - with dropout - two stages of keep-flag records
-constexpr int flbq_lds_bytes(int H, int DT, bool drop) {
-    return (4 + FLB_NK16) * H * DT * 512 + 512 + FLB_NW * 3 * 4 * H * FLB_GWR + (drop ? 2048 : 0);
-}
-// ... of the key-major kernel: the same plus two stages of row constants (1 KB each) and of the waves' D rows
-constexpr int flbk_lds_bytes(int H, int DT, bool drop) {
-    return (4 + FLB_NK16) * H * DT * 512 + 2048 + 2 * FLB_NW * 16 * H * 4 + 512 + FLB_NW * 3 * 4 * H * FLB_GWR + (drop ? 2048 : 0);
-}
-
-static int dispatch_bwdq(const FlashBwdArgs& a, int H, int dh, int nwg, hipStream_t st) {
+// One dispatch for both kernels: the (H, head dim) instance, its LDS need, the launch with or without dropout
+template <bool KEYMAJOR, typename Args>
+static int flb_dispatch(const Args& a, int H, int dh, int nwg, hipStream_t st) {
     return attn_dispatch(H, dh, [&](auto h, auto ds, auto tl) {
         constexpr int HH = decltype(h)::value, DS = decltype(ds)::value, DT = FragDims<DS, decltype(tl)::value>::DT;
         constexpr bool TL = decltype(tl)::value;
-        if constexpr (flbq_lds_bytes(HH, DT, true) > FL_LDS_MAX) return -2;
-        else return fl_launch<FlashBwdArgs, talking_bwdq_kernel<HH, DS, TL, true>, talking_bwdq_kernel<HH, DS, TL, false>>(
-            a, nwg, 64 * FLB_NW, flbq_lds_bytes(HH, DT, false), flbq_lds_bytes(HH, DT, true), a.p_drop > 0.f, st);
+        constexpr int plain = flb_lds(HH, DT, KEYMAJOR, false).bytes, drop = flb_lds(HH, DT, KEYMAJOR, true).bytes;
+        if constexpr (drop > FL_LDS_MAX) return -2;
+        else if constexpr (KEYMAJOR)
+            return fl_launch<Args, talking_bwdk_kernel<HH, DS, TL, true>, talking_bwdk_kernel<HH, DS, TL, false>>(a, nwg, 64 * FLB_NW, plain, drop, a.p_drop > 0.f, st);
+        else
+            return fl_launch<Args, talking_bwdq_kernel<HH, DS, TL, true>, talking_bwdq_kernel<HH, DS, TL, false>>(a, nwg, 64 * FLB_NW, plain, drop, a.p_drop > 0.f, st);
     });
 }
 
@@ -1258,19 +1208,20 @@ extern "C" int spe_talking_bwdq_plan(int B, int N, int nwg, int* steps_per_wg, i
     return 0;
 }
 
-static int bwdq_fill(FlashBwdArgs& a, FlashPlan& p, const void* Qf, const void* dOf, const void* Kf, const void* Vf, const void* K16, const float* Wl,
-                     const float* Ww, const float* c0, int Np, const void* keepbits, int B, int H, int N, int dh, int nwg, float p_drop) {
+// The part of the two entry points that is the same, for either argument struct (the fields it fills have one name in both): the range checks (-2; np_pad:
+// rows of c0 beyond 16 nt that the kernel fetches), the plan, the shared fields
+template <typename Args>
+static int flb_fill(Args& a, FlashPlan& p, const void* Qf, const void* dOf, const void* Kf, const void* Vf, const float* Wl, const float* Ww,
+                    const float* c0, int Np, int np_pad, float* ws_w, const void* keepbits, int B, int N, int dh, int nwg, float p_drop) {
     const int nt = (N + 15) / 16;
-    if (dh < 1 || dh > 64 || nwg <= 0 || Np < nt * 16 || (p_drop > 0.f && !keepbits)) return -2;
+    if (dh < 1 || dh > 64 || nwg <= 0 || Np < nt * 16 + np_pad || (p_drop > 0.f && !keepbits)) return -2;
     p = fl_plan(B, nt, FLB_NW, nt, nwg);
     a.Qf = (const unsigned char*)Qf; a.dOf = (const unsigned char*)dOf; a.Kf = (const unsigned char*)Kf; a.Vf = (const unsigned char*)Vf;
-    a.K16 = (const unsigned char*)K16; a.Wl = Wl; a.Ww = Ww; a.c0 = c0; a.Np = Np; a.Drows = nullptr;
-    a.ws_q = nullptr; a.ws_w = nullptr; a.dS = nullptr;
+    a.Wl = Wl; a.Ww = Ww; a.c0 = c0; a.Np = Np; a.ws_w = ws_w;
     a.keepbits = (p_drop > 0.f) ? reinterpret_cast<const unsigned*>(keepbits) : nullptr;
     a.B = B; a.N = N; a.nt = nt; a.nmaj = p.nmaj; a.spw = p.spw; a.total = p.total; a.p_drop = p_drop;
     return 0;
 }
-
 
 extern "C" int spe_talking_bwdq_pass2(const void* Qf, const void* dOf, const void* Kf, const void* Vf, const void* K16, const float* Wl, const float* Ww,
                                       const float* c0, const float* Drows, int Np, float* ws_q, float* ws_w, void* dS, float* dq, void* dq16,
@@ -1278,11 +1229,11 @@ extern "C" int spe_talking_bwdq_pass2(const void* Qf, const void* dOf, const voi
                                       hipStream_t st) {
     if ((long)B * ((N + 15) / 16) <= 0) return 0;
     FlashBwdArgs a; FlashPlan p;
-    int rc = bwdq_fill(a, p, Qf, dOf, Kf, Vf, K16, Wl, Ww, c0, Np, keepbits, B, H, N, dh, nwg, p_drop);
+    int rc = flb_fill(a, p, Qf, dOf, Kf, Vf, Wl, Ww, c0, Np, 0, ws_w, keepbits, B, N, dh, nwg, p_drop);
     if (rc != 0) return rc;
     if (!ws_q || !ws_w || !dS || !Drows || !K16 || (!dq && !dq16)) return -2;
-    a.ws_q = ws_q; a.ws_w = ws_w; a.dS = reinterpret_cast<unsigned short*>(dS); a.Drows = Drows;
-    rc = dispatch_bwdq(a, H, dh, p.nwg, st);
+    a.K16 = (const unsigned char*)K16; a.ws_q = ws_q; a.dS = reinterpret_cast<unsigned short*>(dS); a.Drows = Drows;
+    rc = flb_dispatch<false>(a, H, dh, p.nwg, st);
     if (rc != 0) return rc;
     const int DT = frag_geom(dh).dt;
     const long nvec = (long)B * p.nmaj * FLB_NW * H * DT * 64;
@@ -1292,22 +1243,11 @@ extern "C" int spe_talking_bwdq_pass2(const void* Qf, const void* dOf, const voi
     return 0;
 }
 
-// ---- key-major pass: dispatch, C-ABI
-static int dispatch_bwdk(const FlashBwdKArgs& a, int H, int dh, int nwg, hipStream_t st) {
-    return attn_dispatch(H, dh, [&](auto h, auto ds, auto tl) {
-        constexpr int HH = decltype(h)::value, DS = decltype(ds)::value, DT = FragDims<DS, decltype(tl)::value>::DT;
-        constexpr bool TL = decltype(tl)::value;
-        if constexpr (flbk_lds_bytes(HH, DT, true) > FL_LDS_MAX) return -2;
-        else return fl_launch<FlashBwdKArgs, talking_bwdk_kernel<HH, DS, TL, true>, talking_bwdk_kernel<HH, DS, TL, false>>(
-            a, nwg, 64 * FLB_NW, flbk_lds_bytes(HH, DT, false), flbk_lds_bytes(HH, DT, true), a.p_drop > 0.f, st);
-    });
-}
-
 // C-ABI: see include/spe_hip.h.  1 when (H, head dim) is in the dispatch and the flash forward and both backward kernels fit the LDS with dropout on.
 extern "C" int spe_talking_fused_supported(int H, int dh) {
     return attn_dispatch(H, dh, [](auto h, auto ds, auto tl) {
         constexpr int HH = decltype(h)::value, DT = FragDims<decltype(ds)::value, decltype(tl)::value>::DT;
-        return (flf_lds_bytes(HH, DT, true) <= FL_LDS_MAX && flbq_lds_bytes(HH, DT, true) <= FL_LDS_MAX && flbk_lds_bytes(HH, DT, true) <= FL_LDS_MAX) ? 0 : -2;
+        return (flf_lds_bytes(HH, DT, true) <= FL_LDS_MAX && flb_lds(HH, DT, false, true).bytes <= FL_LDS_MAX && flb_lds(HH, DT, true, true).bytes <= FL_LDS_MAX) ? 0 : -2;
     }) == 0;
 }
 
@@ -1316,16 +1256,12 @@ extern "C" int spe_talking_bwdk_pass1(const void* Qf, const void* dOf, const voi
                                       long ob, long on, long oh, const void* keepbits, int B, int H, int N, int dh, int nwg, float p_drop, hipStream_t st) {
     const int nt = (N + 15) / 16;
     if ((long)B * nt <= 0) return 0;
-    if (dh < 1 || dh > 64 || nwg <= 0 || Np < nt * 16 + 64 || (p_drop > 0.f && !keepbits)) return -2;
+    FlashBwdKArgs a; FlashPlan p;
+    int rc = flb_fill(a, p, Qf, dOf, Kf, Vf, Wl, Ww, c0, Np, 64, ws_w, keepbits, B, N, dh, nwg, p_drop);
+    if (rc != 0) return rc;
     if (!Qf || !dOf || !dO16 || !Kf || !Vf || !Wl || !Ww || !bw || !c0 || !ws_d || !ws_v || !ws_w || !Drows || (!dv && !dv16)) return -2;
-    const FlashPlan p = fl_plan(B, nt, FLB_NW, nt, nwg);
-    FlashBwdKArgs a;
-    a.Qf = (const unsigned char*)Qf; a.dOf = (const unsigned char*)dOf; a.dO16 = (const unsigned char*)dO16;
-    a.Kf = (const unsigned char*)Kf; a.Vf = (const unsigned char*)Vf; a.Wl = Wl; a.Ww = Ww; a.bw = bw; a.c0 = c0; a.Np = Np;
-    a.ws_d = ws_d; a.ws_v = ws_v; a.ws_w = ws_w;
-    a.keepbits = (p_drop > 0.f) ? reinterpret_cast<const unsigned*>(keepbits) : nullptr;
-    a.B = B; a.N = N; a.nt = nt; a.nmaj = p.nmaj; a.spw = p.spw; a.total = p.total; a.p_drop = p_drop;
-    int rc = dispatch_bwdk(a, H, dh, p.nwg, st);
+    a.dO16 = (const unsigned char*)dO16; a.bw = bw; a.ws_d = ws_d; a.ws_v = ws_v;
+    rc = flb_dispatch<true>(a, H, dh, p.nwg, st);
     if (rc != 0) return rc;
     const long n = (long)B * Np * H;
     hipLaunchKernelGGL(bwdk_rows_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ws_d, Drows, B, H, N, Np, p.nmaj);

@@ -200,6 +200,8 @@ __host__ __device__ static inline FlashPlan fl_plan(int B, int nt_major, int per
     p.nwg = (int)((p.total + spw - 1) / spw);
     return p;
 }
+// the slot of the partial result of a segment of major bm = b * nmaj + mj (device side)
+__device__ __forceinline__ int fl_slot(int bm, int nt, int spw) { return (int)blockIdx.x - (int)(((long)bm * nt) / spw); }
 
 // ---- dropout keep-scales (counter layout: (b, head pair, query, 4-key group), eight 16-bit lots)
 template <int H>

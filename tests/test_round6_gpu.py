@@ -115,7 +115,10 @@ def _fp64_backward(x, b, H, N, p_drop):
 
 CASES = [(2, 8, 4150, 48, 0.0), (2, 8, 4150, 48, 0.05), (1, 8, 6200, 48, 0.0), (1, 8, 6200, 48, 0.1),
          (1, 8, 100, 48, 0.0), (2, 4, 196, 48, 0.0), (2, 8, 1100, 48, 0.1), (1, 4, 300, 32, 0.05), (2, 8, 400, 16, 0.0), (1, 8, 2070, 48, 0.0),
-         (1, 4, 64, 64, 0.2), (1, 8, 100, 32, 0.1), (1, 4, 100, 16, 0.0)]
+         (1, 4, 64, 64, 0.2), (1, 8, 100, 32, 0.1), (1, 4, 100, 16, 0.0),
+         # the other six (H, fragment geometry, dropout) instances of each kernel: 19 tiles (no multiple of the 4 waves), a ragged last tile,
+         # workgroup ranges that cross the majors' boundaries
+         (1, 4, 300, 48, 0.1), (1, 4, 300, 32, 0.0), (1, 8, 300, 16, 0.1), (1, 4, 300, 64, 0.0), (1, 8, 300, 32, 0.0), (1, 4, 300, 16, 0.1)]
 
 
 @pytest.mark.parametrize("B,H,N,dh,p_drop", CASES)

@@ -1,7 +1,7 @@
 """The five attention kernels of one backbone block in isolation at cfg2 (B = 2, H = 8, N = 4150, dh = 48) or another shape, timed with HIP events on the
 launch stream (kernel + its merges per entry point):
 
-    python tools/debug/attn_time.py [B N H dh [p_drop]]                         # the shipped library
+    python tools/debug/attn_time.py [B N H dh [p_drop]] [--rep N]               # the shipped library; N timed repeats per line (default 10)
     SPE_HIP_LIB=build_ab/<name>.so python tools/debug/attn_time.py ...          # a -DSPE_ABLATE variant built by tools/ab.py
 
 Reference: models/cait.py:377-389 and its autograd."""
@@ -15,7 +15,13 @@ sys.path.insert(0, ROOT)
 from spe_amd import kernels as K  # noqa: E402
 
 STAMPS = "--stamps" in sys.argv
-a = [float(x) for x in sys.argv[1:] if not x.startswith("--")]
+argv = sys.argv[1:]
+REP = 10
+if "--rep" in argv:
+    k = argv.index("--rep")
+    REP = int(argv[k + 1])
+    del argv[k:k + 2]
+a = [float(x) for x in argv if not x.startswith("--")]
 B, N, H, dh = (int(a[0]), int(a[1]), int(a[2]), int(a[3])) if len(a) >= 4 else (2, 4150, 8, 48)
 p_drop = a[4] if len(a) >= 5 else 0.0
 dev = torch.device("cuda:0")
@@ -62,7 +68,6 @@ steps = [("statistics + merge (workspace allocated per call)", stats), ("flash f
 for _, f in steps:
     f()
 torch.cuda.synchronize()
-REP = 10
 tot = 0.0
 print(f"library {K.lib.LIBPATH}; B={B} N={N} H={H} dh={dh} p_drop={p_drop}")
 for name, f in steps:
